@@ -30,8 +30,12 @@ The FULL record — everything below — goes to gpurun_out/bench_detail.json (-
                       --full adds torch_rocm_baseline (the reference's own GPU path, stock PyTorch-ROCm), the reference-loss training
                       batch, per-config baselines and the forced single-rank RCCL leg
 The default run (the driver's command) takes ~100 s on an MI355X box; --full several minutes.
+
+--dump-outputs DIR writes what the last timed step returned (dump_outputs): graphs, features and weights are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
+import copy
 import json
 import os
 import socket
@@ -101,7 +105,12 @@ def parse():
     ap.add_argument("--detail-file", default=None,
                     help="where the full record goes (default gpurun_out/bench_detail.json, per workload: bench_detail_<name>.json); stdout "
                          "carries ONE compact JSON line (< 4 KB)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; at most 64 MB in all: "
+                         "beyond that a fixed seeded sample of node rows, listed in DIR/<name>__index.npy)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.full and a.cpu_budget_s == 30.0:
         a.cpu_budget_s = 100.0
     return a
@@ -298,18 +307,21 @@ def main():
         return res[0] if isinstance(res, tuple) else res     # 'S' models also return the transform outputs
 
     def eager_step():
+        """What a caller of the timed path receives: the embeddings, and for 'S' models (embeddings, transform outputs)."""
         if args.graph:
-            return first(runner())
+            return runner()
         if not args.train:
             with torch.no_grad():
-                return first(model(x_list, adj_list))
+                return model(x_list, adj_list)
         opt.zero_grad(set_to_none=True)
-        out = first(model(x_list, adj_list))
-        out.square().mean().backward()
+        res = model(x_list, adj_list)
+        first(res).square().mean().backward()
         if use_dist:
             spp.allreduce_replicated_grads(model)
         opt.step()
-        return out.detach()
+        if torch.is_tensor(res):
+            return res.detach()
+        return res[0].detach(), [None if t is None else t.detach() for t in res[1]]
 
     def fence():
         torch.cuda.synchronize()
@@ -325,6 +337,9 @@ def main():
         # starts at idle clocks and a 20 ms window measured 29 vs 21.5 ms depending on what ran before it (the number of steps
         # this took is on the JSON line as `prewarm_steps`); same count on every rank (decided by rank 0)
         if prewarm_s > 0:
+            # training: the clock decides how many Adam steps the pre-warm takes, so the weights and optimizer state are put back
+            # afterwards — the timed steps then start from the same state in every run (--dump-outputs compares runs)
+            saved = copy.deepcopy((model.state_dict(), opt.state_dict())) if args.train else None
             t0 = time.perf_counter()
             while True:
                 step()
@@ -335,24 +350,37 @@ def main():
                     dist.broadcast(go, src=0)
                 if float(go.item()) == 0.0 or prewarm["steps"] >= 200:
                     break
+            if saved is not None:
+                model.load_state_dict(saved[0])
+                opt.load_state_dict(saved[1])
+                del saved
         for _ in range(warmup):
             step()
         fence()
         launches.clear()
         t_start = time.perf_counter()
         for _ in range(steps):
-            out = step()
+            res = step()
         fence()
         elapsed = time.perf_counter() - t_start
         if use_dist:
             tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
-        return 1000.0 * elapsed / steps, out
+        return 1000.0 * elapsed / steps, res
 
     copy_bw = measure_copy_bandwidth(dev) if rank == 0 else None
-    ms_per_step, out = timed(args.steps, args.warmup, prewarm_s=args.prewarm_s)
+    ms_per_step, res = timed(args.steps, args.warmup, prewarm_s=args.prewarm_s)
+    out = first(res)
     assert torch.isfinite(out).all()
+    if args.dump_outputs:
+        arrays = {"embeddings": out}
+        if not torch.is_tensor(res):
+            arrays.update(("transform_t%02d" % t, tr) for t, tr in enumerate(res[1]) if tr is not None)
+        if world > 1:
+            arrays = {"%s_rank%d" % (k, rank): v for k, v in arrays.items()}
+        dump_outputs(args.dump_outputs, arrays, DUMP_BYTES // world, log)
+    del res
     per_rank_ms = None
     if use_dist:
         # DESIGN §5's model, line by line: every rank's compute / exposed exchange / temporal head over the timed steps
@@ -370,7 +398,7 @@ def main():
         os.environ["CTGCN_STREAMS"] = "1"
         try:
             roof_steps = 2
-            _, out1 = timed(roof_steps, 1)
+            out1 = first(timed(roof_steps, 1)[1])
             assert torch.equal(out1, out)                 # same kernels, same inputs
             recorded = list(launches)
             roof_pass = "a separate single-stream pass (CTGCN_STREAMS=1, %d steps) after the timed multi-stream steps" % roof_steps
@@ -564,6 +592,7 @@ def main():
         os.environ["CTGCN_FP32_MFMA_ONLY"] = "1"
         try:
             ms_exact, out_exact = timed(max(2, min(3, args.steps)), 1)
+            out_exact = first(out_exact)
         finally:
             if prev is None:
                 del os.environ["CTGCN_FP32_MFMA_ONLY"]
@@ -734,6 +763,37 @@ def main():
 
 MAX_LINE_BYTES = 4096       # the driver keeps ~9 KB of stdout: round 5's 23 KB line did not parse there
 T_START = time.time()
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: size of all files written, .npy headers included
+DUMP_SEED = 20261015
+
+
+def dump_outputs(path, arrays, budget, log):
+    """{name: tensor} -> path/<name>.npy, float64 kept, anything else as float32.  When the arrays would take more than `budget` bytes,
+    each keeps the rows of one fixed seeded sample along its largest axis (the node axis of every CTGCN output), the same rows for
+    arrays with as many nodes, and path/<name>__index.npy lists them (float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    header = 128                                                    # an .npy header of these shapes is 128 bytes
+    itemsize = {k: 8 if t.dtype == torch.float64 else 4 for k, t in arrays.items()}
+    axis = {k: max(range(t.dim()), key=lambda i: t.shape[i]) for k, t in arrays.items()}
+    full = sum(t.numel() * itemsize[k] + header for k, t in arrays.items())
+    # bytes per sampled row: the row itself + its index
+    per_row = {k: t.numel() // max(1, t.shape[axis[k]]) * itemsize[k] + 8 for k, t in arrays.items()}
+    frac = 1.0 if full <= budget else (budget - 2 * header * len(arrays)) / sum(t.shape[axis[k]] * per_row[k] for k, t in arrays.items())
+    written = 0
+    for k, t in arrays.items():
+        dtype = torch.float64 if itemsize[k] == 8 else torch.float32
+        if frac < 1.0:
+            rows = t.shape[axis[k]]
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=int(rows * frac), replace=False))
+            t = t.index_select(axis[k], torch.from_numpy(idx).to(t.device))
+            np.save(os.path.join(path, k + "__index.npy"), idx.astype(np.float64))
+            written += os.path.getsize(os.path.join(path, k + "__index.npy"))
+        np.save(os.path.join(path, k + ".npy"), t.detach().to(dtype).cpu().numpy())
+        written += os.path.getsize(os.path.join(path, k + ".npy"))
+    assert written <= budget, "dumped %d bytes, budget %d" % (written, budget)
+    log("outputs of the last timed step: %s (%s, %d bytes)" % (path, "full" if frac == 1.0 else "%.4f of the rows" % frac, written))
 
 
 def _pick(d, keys):

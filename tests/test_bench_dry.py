@@ -67,3 +67,34 @@ def test_bench_under_the_drivers_launcher_dry():
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     _check(p.stdout, 3)
+
+
+def test_dump_outputs_full_and_sampled(tmp_path):
+    """bench.dump_outputs (--dump-outputs): small outputs are written whole; larger ones keep the same seeded rows of every array along its
+    node axis, stay within the byte budget, and are the same files from run to run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    emb = torch.randn(4, 5000, 16, generator=g)                      # [T, nodes, d], as CTGCN returns it
+    trans = torch.randn(5000, 8, generator=g, dtype=torch.float64)   # [nodes, d]
+    arrays = {"embeddings": emb, "transform_t00": trans}
+    bench.dump_outputs(str(tmp_path / "full"), arrays, bench.DUMP_BYTES, lambda *a: None)
+    assert sorted(os.listdir(tmp_path / "full")) == ["embeddings.npy", "transform_t00.npy"]
+    got = np.load(tmp_path / "full" / "embeddings.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, emb.numpy())
+    got = np.load(tmp_path / "full" / "transform_t00.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, trans.numpy())
+    budget = 200_000
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget, lambda *a: None)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= budget
+    for name in ("embeddings", "transform_t00", "embeddings__index", "transform_t00__index"):
+        assert (tmp_path / "a" / (name + ".npy")).read_bytes() == (tmp_path / "b" / (name + ".npy")).read_bytes(), name
+    idx = np.load(tmp_path / "a" / "embeddings__index.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "a" / "transform_t00__index.npy"))
+    rows = idx.astype(np.int64)
+    assert 0 < len(rows) < 5000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "embeddings.npy"), emb.numpy()[:, rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "transform_t00.npy"), trans.numpy()[rows])
