@@ -10,5 +10,8 @@ from .core_adj import CoreAdj  # noqa: F401
 from .layers import CoreDiffusion, MLP  # noqa: F401
 from .models import CDN, CGCN, CTGCN  # noqa: F401
 from .helper import DataLoader  # noqa: F401
+from .metrics import NegativeSamplingLoss, ReconstructionLoss  # noqa: F401
+from .embedding import UnsupervisedEmbedding  # noqa: F401
 
-__all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoader"]
+__all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoader", "NegativeSamplingLoss", "ReconstructionLoss",
+           "UnsupervisedEmbedding"]

@@ -14,7 +14,7 @@ ACT_NONE, ACT_SELU = 0, 1
 OP_KCORE = 1
 OP_INGEST = 2
 MAX_SLOTS = 255
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _c = ctypes
 _vp, _i64, _i32, _u32, _int, _sz = _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_uint32, _c.c_int, _c.c_size_t
@@ -91,6 +91,14 @@ SIGNATURES = {
     "ctgcn_row_cumsum_f32": (_int, [_i64, _vp, _vp, _vp, _vp]),
     "ctgcn_random_walk_pairs": (_int, [_i64, _vp, _vp, _vp, _i32, _i32, _i32, _c.c_uint64, _int, _vp, _vp, _vp, _vp]),
     "ctgcn_neg_sampling_indices": (_int, [_i64, _vp, _vp, _vp, _i32, _i64, _vp, _c.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctgcn_epoch_scan_workspace_bytes": (_sz, [_i64]),
+    "ctgcn_neg_sampling_offsets_batched": (_int, [_i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_neg_sampling_indices_batched": (_int, [_i64, _vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctgcn_negsampling_loss_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "ctgcn_negsampling_loss_fwd_bwd_f32": (_int, [_i64, _i64, _i64, _i32, _i32, _c.c_float, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "ctgcn_reconstruction_loss_workspace_bytes": (_sz, [_i64]),
+    "ctgcn_reconstruction_loss_fwd_bwd_f32": (_int, [_i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
     "ctgcn_write_embedding_tsv": (_int, [_c.c_char_p, _i64, _i32, _vp, _i64, _c.c_char_p, _vp, _c.c_char, _i32]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }

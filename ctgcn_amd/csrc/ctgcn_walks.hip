@@ -10,22 +10,11 @@
 #include <cstdio>
 
 #include "../../include/ctgcn_hip.h"
+#include "ctgcn_rng.h"
 
 extern "C" int ctgcn_set_error_(int code, const char *msg);
 
 namespace {
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
-{
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ double u01(uint64_t a, uint64_t b, uint64_t c)
-{
-    return (double)(mix64(mix64(a) ^ mix64(b * 0x100000001b3ull + c)) >> 11) * (1.0 / 9007199254740992.0);
-}
 
 constexpr int MAX_WALK = 32;      // walk_length + 1 <= 32
 
@@ -47,7 +36,7 @@ __global__ __launch_bounds__(256) void walk_kernel(int64_t n, int walk_len, int 
         const int cur = walk[len - 1];
         const int s = row_ptr[cur], e = row_ptr[cur + 1];
         if (e == s) break;                                              // random_walk.py:29-30: dead end
-        const double u = u01(seed, (uint64_t)node * 1000003ull + (uint64_t)it, (uint64_t)len);
+        const double u = ctgcn_u01(seed, (uint64_t)node * 1000003ull + (uint64_t)it, (uint64_t)len);
         int pick;
         if (weighted) {
             const float target = (float)(u * (double)cumw[e - 1]);
@@ -103,7 +92,7 @@ __global__ __launch_bounds__(256) void pos_sample_kernel(int64_t batch, const in
     int64_t o = offsets[b];
     int need = min(deg, num);
     for (int k = 0; k < deg && need > 0; ++k) {
-        const bool take = (deg <= num) || (u01(seed, (uint64_t)b, (uint64_t)k) * (double)(deg - k) < (double)need);
+        const bool take = (deg <= num) || (ctgcn_u01(seed, (uint64_t)b, (uint64_t)k) * (double)(deg - k) < (double)need);
         if (take) { node_out[o] = v; pos_out[o] = col[s + k]; ++o; --need; }
     }
 }
@@ -115,7 +104,7 @@ __global__ void neg_sample_kernel(int64_t table_len, const int32_t *__restrict__
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     int got = 0;
     for (uint64_t tries = 0; got < num; ++tries) {
-        const int64_t p = min((int64_t)(u01(seed, 0x5eedull, tries) * (double)table_len), table_len - 1);
+        const int64_t p = min((int64_t)(ctgcn_u01(seed, 0x5eedull, tries) * (double)table_len), table_len - 1);
         bool dup = false;
         for (int i = 0; i < got; ++i) dup |= (pos_scratch[i] == p);
         if (!dup) { pos_scratch[got] = p; neg_out[got] = table[p]; ++got; }

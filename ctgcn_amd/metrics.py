@@ -1,8 +1,11 @@
-"""NegativeSamplingLoss with the reference's constructor / forward signature (reference metrics.py:18-93).
+"""NegativeSamplingLoss and ReconstructionLoss with the reference's constructor / forward signatures (reference metrics.py:18-123).
 
 The reference walks over the batch nodes in Python, drawing positives with random.sample per node (metrics.py:68-84) —
 the bottleneck of real training once the model is fast.  Here the draws are one HIP kernel
 (ctgcn_neg_sampling_indices); the scores and the BCE terms are the reference's own formulas in torch.
+
+epoch_loss() of both losses is the epoch-fused path of embedding.UnsupervisedEmbedding: every batch of an epoch scored
+against ONE forward's embeddings, losses and the gradient of their sum by the kernels of ctgcn_epoch.hip.
 """
 import ctypes
 import itertools
@@ -20,6 +23,40 @@ from .walks import WalkPairs
 # forward, metrics.py:69) advanced by a counter, so runs, and the ranks of one job, draw different samples
 _seed_base = int.from_bytes(os.urandom(8), "little")
 _seed_counter = itertools.count(1)
+_M64 = 2 ** 64 - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _splitmix64(z):
+    z = (z + _GOLDEN) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def epoch_batch_seed(base, epoch, batch, snapshot):
+    """The sample seed of (epoch, batch, snapshot) under a run's base seed: the same in the fused and the per-batch trainer."""
+    z = _splitmix64(base & _M64)
+    for v in (epoch, batch, snapshot):
+        z = _splitmix64(z ^ (v & _M64))
+    return z
+
+
+def _seed_tensor(seeds, device):
+    """uint64 seeds as the bits of an int64 device tensor."""
+    return torch.from_numpy(np.asarray([int(x) & _M64 for x in seeds], dtype=np.uint64).view(np.int64)).to(device)
+
+
+def _rows(mat, what):
+    """(pointer, leading dimension) of a [N, d] fp32 CUDA view whose rows are unit-stride (a [T, N, d] view of [N, T, d] qualifies)."""
+    ops._need_cuda(mat)
+    if mat.dim() != 2 or mat.dtype != torch.float32 or (mat.shape[1] > 1 and mat.stride(1) != 1):
+        raise ValueError("%s must be a float32 [N, d] view with unit column stride" % what)
+    return mat.data_ptr(), max(mat.stride(0), mat.shape[1])
+
+
+def _as_list(x):
+    return [x] if not isinstance(x, list) and x.dim() == 2 else list(x)
 
 
 class NegativeSamplingLoss(nn.Module):
@@ -47,8 +84,9 @@ class NegativeSamplingLoss(nn.Module):
             hit = self._cache[(i, str(device))] = (pairs, table.to(device=device, dtype=torch.int32).contiguous())
         return hit
 
-    def sample_indices(self, i, batch_indices):
-        """(sample_num, node_indices, pos_indices, neg_indices) — metrics.py:62-93 for snapshot i."""
+    def sample_indices(self, i, batch_indices, seed=None):
+        """(sample_num, node_indices, pos_indices, neg_indices) — metrics.py:62-93 for snapshot i.  seed: an explicit draw seed
+        (the trainer's per-(epoch, batch, snapshot) seed); None: the loss's own stream."""
         device = batch_indices.device
         ops._need_cuda(batch_indices)
         pairs, table = self._device_inputs(i, device)
@@ -64,7 +102,9 @@ class NegativeSamplingLoss(nn.Module):
         pos_idx = torch.empty(sample_num, dtype=torch.int64, device=device)
         neg_idx = torch.empty(num, dtype=torch.int64, device=device)
         scratch = torch.empty(num, dtype=torch.int64, device=device)
-        if self.seed is not None:
+        if seed is not None:
+            pass
+        elif self.seed is not None:
             seed = self.seed * 1000003 + i
         elif self.shared_base is not None:          # every rank makes the same sequence of calls: the same draws everywhere
             self._shared_calls += 1
@@ -79,7 +119,8 @@ class NegativeSamplingLoss(nn.Module):
         dt = batch_indices.dtype
         return sample_num, node_idx.to(dt), pos_idx.to(dt), neg_idx.to(dt)
 
-    def forward(self, input_list):
+    def forward(self, input_list, seeds=None):
+        """seeds (optional): one explicit draw seed per snapshot (see sample_indices)."""
         assert len(input_list) == 2
         node_embedding, batch_indices = input_list[0], input_list[1]
         if not isinstance(node_embedding, list) and node_embedding.dim() == 2:
@@ -88,10 +129,123 @@ class NegativeSamplingLoss(nn.Module):
         loss = torch.zeros(1, device=batch_indices.device)
         for i in range(len(node_embedding)):
             emb = node_embedding[i]
-            sample_num, node_idx, pos_idx, neg_idx = self.sample_indices(i, batch_indices)
+            sample_num, node_idx, pos_idx, neg_idx = self.sample_indices(i, batch_indices, None if seeds is None else seeds[i])
             if sample_num == 0:
                 continue
             pos_score = torch.sum(emb[node_idx].mul(emb[pos_idx]), dim=1)
             neg_score = torch.sum(emb[node_idx].matmul(torch.transpose(emb[neg_idx], 1, 0)), dim=1)
             loss = loss + bce(pos_score, torch.ones_like(pos_score)) + self.Q * bce(neg_score, torch.zeros_like(neg_score))
         return loss
+
+    def batched_sample_indices(self, i, node_indices, batch_size, seeds):
+        """The draws of every batch of an epoch for snapshot i in two launches and one host read (the total, for allocation).
+        node_indices: the epoch permutation (int64, CUDA); batch b = node_indices[b*batch_size : (b+1)*batch_size] draws with
+        seeds[b] exactly what sample_indices(i, batch, seed=seeds[b]) draws.  Returns (total, offsets int64[P+1] per position,
+        batch_offsets int64[B+1], node_idx int64[total], pos_idx int64[total], neg_idx int64[B, num]); node_idx / pos_idx are
+        None when total == 0."""
+        device = node_indices.device
+        ops._need_cuda(node_indices)
+        pairs, table = self._device_inputs(i, device)
+        num = int(self.neg_sample_num)
+        perm = node_indices.to(torch.int64).contiguous()
+        P = perm.numel()
+        B = -(-P // batch_size)
+        if len(seeds) != B:
+            raise ValueError("one seed per batch: %d batches, %d seeds" % (B, len(seeds)))
+        lib = _lib.load()
+        offsets = torch.empty(P + 1, dtype=torch.int64, device=device)
+        batch_off = torch.empty(B + 1, dtype=torch.int64, device=device)
+        neg_idx = torch.empty(B, num, dtype=torch.int64, device=device)
+        scratch = torch.empty(B, num, dtype=torch.int64, device=device)
+        seed_t = _seed_tensor(seeds, device)
+        with torch.cuda.device(device):
+            ws = torch.empty(max(lib.ctgcn_epoch_scan_workspace_bytes(P), 1), dtype=torch.uint8, device=device)
+            check(lib.ctgcn_neg_sampling_offsets_batched(P, ptr(perm), ptr(pairs.row_ptr), num, batch_size, ptr(offsets), ptr(batch_off),
+                                                         ptr(ws), ws.numel(), ops._stream()), "ctgcn_neg_sampling_offsets_batched")
+            total = int(offsets[P].item())
+            node_idx = torch.empty(total, dtype=torch.int64, device=device) if total else None
+            pos_idx = torch.empty(total, dtype=torch.int64, device=device) if total else None
+            check(lib.ctgcn_neg_sampling_indices_batched(P, ptr(perm), batch_size, ptr(seed_t), ptr(pairs.row_ptr), ptr(pairs.col), num,
+                                                         table.numel(), ptr(table), ptr(offsets), ptr(node_idx), ptr(pos_idx), ptr(neg_idx),
+                                                         ptr(scratch), ops._stream()), "ctgcn_neg_sampling_indices_batched")
+        return total, offsets, batch_off, node_idx, pos_idx, neg_idx
+
+    def epoch_loss(self, embeddings, node_indices, batch_size, seeds, grads):
+        """Every batch of an epoch against one set of embeddings: returns the per-batch losses float64 [T, B] (the reference's
+        forward of batch b, snapshot t, on these embeddings) and ACCUMULATES d(Σ losses)/dE into grads.  embeddings / grads: a
+        [T, N, d] tensor (a strided view is read in place) or a list of [N, d]; seeds[t][b]: the draw seed of batch b, snapshot t."""
+        emb, grd = _as_list(embeddings), _as_list(grads)
+        if len(emb) != len(grd) or len(seeds) != len(emb):
+            raise ValueError("embeddings, grads and seeds must cover the same snapshots")
+        device = node_indices.device
+        P = node_indices.numel()
+        B = -(-P // batch_size)
+        losses = torch.zeros(len(emb), B, dtype=torch.float64, device=device)
+        lib = _lib.load()
+        for t, (e, g) in enumerate(zip(emb, grd)):
+            e = e.detach()
+            if e.shape != g.shape or e.shape[0] < P:
+                raise ValueError("snapshot %d: embedding %s / gradient %s" % (t, tuple(e.shape), tuple(g.shape)))
+            pe, lde = _rows(e, "embedding")
+            pg, ldg = _rows(g, "gradient")
+            total, offsets, _, node_idx, pos_idx, neg_idx = self.batched_sample_indices(t, node_indices, batch_size, seeds[t])
+            pos_sorted, pos_order = torch.sort(pos_idx, stable=True) if total else (None, None)
+            neg_sorted, neg_order = torch.sort(neg_idx.view(-1), stable=True)
+            d = e.shape[1]
+            with torch.cuda.device(device):
+                ws = torch.empty(lib.ctgcn_negsampling_loss_workspace_bytes(P, total, batch_size, d), dtype=torch.uint8, device=device)
+                check(lib.ctgcn_negsampling_loss_fwd_bwd_f32(P, batch_size, total, d, int(self.neg_sample_num), float(self.Q), pe, lde,
+                                                             ptr(offsets), ptr(node_idx), ptr(pos_idx), ptr(neg_idx), ptr(pos_sorted),
+                                                             ptr(pos_order), ptr(neg_sorted), ptr(neg_order), ptr(losses[t]), pg, ldg,
+                                                             ptr(ws), ws.numel(), ops._stream()), "ctgcn_negsampling_loss_fwd_bwd_f32")
+        return losses
+
+
+class ReconstructionLoss(nn.Module):
+    """Reconstruction loss of CGCN-S / CTGCN-S (reference metrics.py:97-123): Σ_t MSE(structure_t[batch], embedding_t[batch])."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, input_list):
+        assert len(input_list) == 3
+        node_embedding, structure_embedding, batch_indices = input_list[0], input_list[1], input_list[2]
+        node_embedding = _as_list(node_embedding)
+        structure_embedding = _as_list(structure_embedding)
+        mse_loss = nn.MSELoss()
+        structure_loss = 0
+        for embedding_mat, structure_mat in zip(node_embedding, structure_embedding):
+            if batch_indices is not None:
+                structure_loss = structure_loss + mse_loss(structure_mat[batch_indices], embedding_mat[batch_indices])
+            else:
+                structure_loss = structure_loss + mse_loss(structure_mat, embedding_mat)
+        return structure_loss
+
+    def epoch_loss(self, embeddings, structures, node_indices, batch_size, grad_embeddings, grad_structures):
+        """Every batch of an epoch at once: per-batch losses float64 [T, B]; the gradients of their sum are ACCUMULATED into
+        grad_embeddings / grad_structures (same layouts as the inputs; a [T, N, d] strided view is read in place).  node_indices
+        must hold distinct rows."""
+        emb, st, ge, gs = _as_list(embeddings), _as_list(structures), _as_list(grad_embeddings), _as_list(grad_structures)
+        if not (len(emb) == len(st) == len(ge) == len(gs)):
+            raise ValueError("embeddings, structures and gradients must cover the same snapshots")
+        device = node_indices.device
+        ops._need_cuda(node_indices)
+        rows = node_indices.to(torch.int64).contiguous()
+        P = rows.numel()
+        B = -(-P // batch_size)
+        losses = torch.zeros(len(emb), B, dtype=torch.float64, device=device)
+        lib = _lib.load()
+        with torch.cuda.device(device):
+            ws = torch.empty(max(lib.ctgcn_reconstruction_loss_workspace_bytes(P), 1), dtype=torch.uint8, device=device)
+            for t in range(len(emb)):
+                e, s = emb[t].detach(), st[t].detach()
+                if not (e.shape == s.shape == ge[t].shape == gs[t].shape):
+                    raise ValueError("snapshot %d: shapes differ" % t)
+                pe, lde = _rows(e, "embedding")
+                ps, lds = _rows(s, "structure")
+                pge, ldge = _rows(ge[t], "embedding gradient")
+                pgs, ldgs = _rows(gs[t], "structure gradient")
+                check(lib.ctgcn_reconstruction_loss_fwd_bwd_f32(P, batch_size, e.shape[1], ptr(rows), ps, lds, pe, lde, ptr(losses[t]), pgs, ldgs,
+                                                                pge, ldge, ptr(ws), ws.numel(), ops._stream()),
+                      "ctgcn_reconstruction_loss_fwd_bwd_f32")
+        return losses

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CTGCN_ABI_VERSION 28
+#define CTGCN_ABI_VERSION 29
 
 enum {
     CTGCN_OK = 0,
@@ -552,6 +552,54 @@ int ctgcn_neg_sampling_indices(int64_t batch, const int64_t *batch_nodes, const 
                                const int32_t *pair_col, int32_t num, int64_t table_len, const int32_t *neg_table,
                                uint64_t seed, const int64_t *offsets, int64_t *node_out, int64_t *pos_out,
                                int64_t *neg_out, int64_t *scratch, void *stream);
+
+/*
+ * One epoch of the reference's unsupervised schedule (embedding.py:330-368), per snapshot (ABI 29).  Positions p = 0..P-1 index the
+ * epoch's node permutation perm (int64, distinct node ids); batch b holds positions [b*batch_size, min((b+1)*batch_size, P)), and there
+ * are B = ceil(P / batch_size) batches.
+ *
+ * ctgcn_neg_sampling_offsets_batched: offsets[p] (int64[P+1]) = exclusive scan of min(deg(perm[p]), num) over the pair CSR, offsets[P]
+ * = the total sample count (the one value a caller reads back to allocate); batch_offsets[b] (int64[B+1]) = offsets[b*batch_size],
+ * batch_offsets[B] = the total.  workspace: ctgcn_epoch_scan_workspace_bytes(P).
+ * ctgcn_neg_sampling_indices_batched: the draws of all batches; batch b's node / positive / negative indices are identical to what
+ * ctgcn_neg_sampling_indices returns for that batch alone with seed seeds[b] (seeds: device uint64[B]).  Samples are laid out batch
+ * after batch at node_out/pos_out[offsets[p] ...]; neg_out and scratch are int64[B, num].  node_out/pos_out may be NULL when
+ * offsets[P] == 0.
+ */
+size_t ctgcn_epoch_scan_workspace_bytes(int64_t positions);
+int ctgcn_neg_sampling_offsets_batched(int64_t positions, const int64_t *perm, const int32_t *pair_row_ptr, int32_t num,
+                                       int64_t batch_size, int64_t *offsets, int64_t *batch_offsets, void *workspace,
+                                       size_t workspace_bytes, void *stream);
+int ctgcn_neg_sampling_indices_batched(int64_t positions, const int64_t *perm, int64_t batch_size, const uint64_t *seeds,
+                                       const int32_t *pair_row_ptr, const int32_t *pair_col, int32_t num, int64_t table_len,
+                                       const int32_t *neg_table, const int64_t *offsets, int64_t *node_out, int64_t *pos_out,
+                                       int64_t *neg_out, int64_t *scratch, void *stream);
+
+/*
+ * The negative-sampling loss (metrics.py:38-66) of all B batches of one snapshot, forward and backward.  E: the snapshot's embeddings,
+ * row v at E + v*lde (d <= 512).  With the outputs of the two calls above (`samples` = offsets[P]) and n_b the sample count of batch b:
+ *   loss_out[b] = mean_s softplus(-e_u·e_v) + Q · mean_s softplus(e_u·S_b),  S_b = Σ_j E[neg[b, j]]   (double[B]; 0 when n_b = 0)
+ * and dE (row v at dE + v*ldg) is ACCUMULATED with the gradient of Σ_b loss_b.  pos_sorted / pos_order: the positives pos_idx sorted
+ * stably and the sample index of each; neg_sorted / neg_order: the same for the B*num flattened negatives.  Every row of dE is written
+ * by one wave per kernel, no atomics: two calls give bit-identical dE.  workspace: ctgcn_negsampling_loss_workspace_bytes.
+ */
+size_t ctgcn_negsampling_loss_workspace_bytes(int64_t positions, int64_t samples, int64_t batch_size, int32_t d);
+int ctgcn_negsampling_loss_fwd_bwd_f32(int64_t positions, int64_t batch_size, int64_t samples, int32_t d, int32_t num, float Q,
+                                       const float *E, int64_t lde, const int64_t *offsets, const int64_t *node_idx,
+                                       const int64_t *pos_idx, const int64_t *neg_idx, const int64_t *pos_sorted,
+                                       const int64_t *pos_order, const int64_t *neg_sorted, const int64_t *neg_order,
+                                       double *loss_out, float *dE, int64_t ldg, void *workspace, size_t workspace_bytes,
+                                       void *stream);
+
+/*
+ * The reconstruction loss of CGCN-S / CTGCN-S (metrics.py:111-123) under the epoch partition, one snapshot: row r = rows[p] of batch b
+ * has weight w = 1 / (|b| d); loss_out[b] = Σ_{p in b} w ||S[r] - E[r]||² (double[B]), and dS[r] += 2 w (S[r] - E[r]), dE[r] -= the
+ * same (either gradient may be NULL).  rows must be distinct.  workspace: ctgcn_reconstruction_loss_workspace_bytes(P).
+ */
+size_t ctgcn_reconstruction_loss_workspace_bytes(int64_t positions);
+int ctgcn_reconstruction_loss_fwd_bwd_f32(int64_t positions, int64_t batch_size, int32_t d, const int64_t *rows, const float *S,
+                                          int64_t lds, const float *E, int64_t lde, double *loss_out, float *dS, int64_t ldds,
+                                          float *dE, int64_t ldde, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * HOST function (no GPU work): write one snapshot's embedding [n, d] float32 (host pointer, leading dimension ld) as
