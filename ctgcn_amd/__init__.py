@@ -12,6 +12,7 @@ from .models import CDN, CGCN, CTGCN  # noqa: F401
 from .helper import DataLoader  # noqa: F401
 from .metrics import NegativeSamplingLoss, ReconstructionLoss  # noqa: F401
 from .embedding import UnsupervisedEmbedding  # noqa: F401
+from .evaluation import DataGenerator, LinkPredictor, aggregate_results, evaluate, evaluate_window, link_prediction  # noqa: F401
 
 __all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoader", "NegativeSamplingLoss", "ReconstructionLoss",
-           "UnsupervisedEmbedding"]
+           "UnsupervisedEmbedding", "DataGenerator", "LinkPredictor", "aggregate_results", "evaluate", "evaluate_window", "link_prediction"]

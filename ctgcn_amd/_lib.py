@@ -14,7 +14,7 @@ ACT_NONE, ACT_SELU = 0, 1
 OP_KCORE = 1
 OP_INGEST = 2
 MAX_SLOTS = 255
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _c = ctypes
 _vp, _i64, _i32, _u32, _int, _sz = _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_uint32, _c.c_int, _c.c_size_t
@@ -100,6 +100,12 @@ SIGNATURES = {
     "ctgcn_reconstruction_loss_workspace_bytes": (_sz, [_i64]),
     "ctgcn_reconstruction_loss_fwd_bwd_f32": (_int, [_i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
     "ctgcn_write_embedding_tsv": (_int, [_c.c_char_p, _i64, _i32, _vp, _i64, _c.c_char_p, _vp, _c.c_char, _i32]),
+    "ctgcn_lp_neg_sample": (_int, [_i64, _i64, _vp, _i64, _c.c_uint64, _i64, _vp, _vp, _vp, _vp]),
+    "ctgcn_lp_grad_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "ctgcn_lp_grad_f32": (_int, [_i64, _i32, _i32, _u32, _i64, _vp, _i64, _vp, _vp, _vp, _c.c_double, _c.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_lp_hess_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "ctgcn_lp_hess_f32": (_int, [_i64, _i32, _i32, _u32, _i64, _vp, _i64, _vp, _vp, _vp, _c.c_double, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_lp_scores_f32": (_int, [_i64, _i32, _i32, _u32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

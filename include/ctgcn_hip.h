@@ -28,14 +28,15 @@
 extern "C" {
 #endif
 
-#define CTGCN_ABI_VERSION 29
+#define CTGCN_ABI_VERSION 30
 
 enum {
     CTGCN_OK = 0,
     CTGCN_E_INVALID = -1,   /* bad argument (null pointer, negative size, K out of range ...) */
     CTGCN_E_HIP = -2,       /* a HIP runtime call failed; see ctgcn_last_error()              */
     CTGCN_E_WORKSPACE = -3, /* workspace too small                                            */
-    CTGCN_E_UNSUPPORTED = -4
+    CTGCN_E_UNSUPPORTED = -4,
+    CTGCN_E_LIMIT = -5      /* an iteration cap was reached (ctgcn_lp_neg_sample)             */
 };
 
 /* flags of ctgcn_core_aggregate_f32 / ctgcn_core_aggregate_bwd_f32 */
@@ -611,6 +612,42 @@ int ctgcn_reconstruction_loss_fwd_bwd_f32(int64_t positions, int64_t batch_size,
 int ctgcn_write_embedding_tsv(const char *path_host, int64_t n, int32_t d, const float *data_host, int64_t ld,
                               const char *names_blob_host, const int64_t *name_offsets_host, char sep,
                               int32_t threads);
+
+/*
+ * Link-prediction evaluation (evaluation/link_prediction.py; ctgcn_amd/evaluation/), ctgcn_eval.hip.
+ *
+ * ctgcn_lp_neg_sample: count negative edges (from_out[s], to_out[s]), s = 0..count-1, of a snapshot whose membership set is keys:
+ * sorted unique int64 u*n_nodes + v, both directions of every edge.  Slot s draws uniform ordered pairs keyed on (seed, s, attempt)
+ * until u != v and neither direction is in keys, so the output depends only on (seed, s).  A slot still without a pair after
+ * max_attempts draws sets *flag (device int32) and the call returns CTGCN_E_LIMIT.  The call reads the flag back and therefore
+ * synchronises `stream`.  n_nodes <= 3037000499 (keys fit in int64).
+ *
+ * The edge passes below evaluate `models` (<= 16) logistic-regression models on n edges (src[e], dst[e]) of the embedding E
+ * (row v at E + v*lde, 1 <= d <= 256).  Model m uses the edge feature φ = measure_m(E[src], E[dst]), measure_m = bits 2m..2m+1 of
+ * `measures` (0 Avg (a+b)/2, 1 Had a*b, 2 L1 |a-b|, 3 L2 (a-b)^2), and the parameters (w, b) = W[m*(d+1) .. +d], z = w·φ + b.
+ * ctgcn_lp_grad_f32 and ctgcn_lp_scores_f32 take W as float[2, models, d+1]: hi then lo parts (W_hi + W_lo = the fp64 parameters;
+ * lo may be zero), so z carries no systematic fp32 rounding of w.  ctgcn_lp_hess_f32 takes float[models, d+1].
+ * Features are formed in registers and never stored.  label: uint8 {0,1}; s_e = w_pos or w_neg by label.  Node indices outside
+ * [0, n_nodes) read as zero rows.  All reductions are per-block partials summed in a fixed order: repeated calls are bit-identical.
+ *
+ * ctgcn_lp_grad_f32: loss_out[m] = Σ_e s_e softplus(∓z) (double[models]), grad_out[m*(d+1) + j] = Σ_e s_e (σ(z_e) - y_e) φ̃_j with
+ *   φ̃ = (φ, 1) (double[models, d+1]).  fp32 within a 32-edge tile, fp64 across tiles.  workspace: ctgcn_lp_grad_workspace_bytes.
+ * ctgcn_lp_hess_f32: hess_out[m] = Σ_e s_e σ(1-σ) φ̃ φ̃ᵀ (double[models, d+1, d+1], symmetric); fp32 over parts of n/64 edges,
+ *   fp64 across parts.  workspace: ctgcn_lp_hess_workspace_bytes.
+ * ctgcn_lp_scores_f32: score_out[m*n + e] = z (float[models, n]).
+ */
+int ctgcn_lp_neg_sample(int64_t count, int64_t n_nodes, const int64_t *keys, int64_t n_keys, uint64_t seed, int64_t max_attempts,
+                        int64_t *from_out, int64_t *to_out, int32_t *flag, void *stream);
+size_t ctgcn_lp_grad_workspace_bytes(int64_t n, int32_t d, int32_t models);
+int ctgcn_lp_grad_f32(int64_t n, int32_t d, int32_t models, uint32_t measures, int64_t n_nodes, const float *E, int64_t lde,
+                      const int64_t *src, const int64_t *dst, const uint8_t *label, double w_neg, double w_pos, const float *W,
+                      double *loss_out, double *grad_out, void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_lp_hess_workspace_bytes(int64_t n, int32_t d, int32_t models);
+int ctgcn_lp_hess_f32(int64_t n, int32_t d, int32_t models, uint32_t measures, int64_t n_nodes, const float *E, int64_t lde,
+                      const int64_t *src, const int64_t *dst, const uint8_t *label, double w_neg, double w_pos, const float *W,
+                      double *hess_out, void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_lp_scores_f32(int64_t n, int32_t d, int32_t models, uint32_t measures, int64_t n_nodes, const float *E, int64_t lde,
+                        const int64_t *src, const int64_t *dst, const float *W, float *score_out, void *stream);
 
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
