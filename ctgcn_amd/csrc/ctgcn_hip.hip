@@ -2734,7 +2734,7 @@ __device__ __forceinline__ void gru_layer8_h2_body(const LayerArgs &a, const int
     __shared__ float csc_hh[4][GRU_H];                   // rows 0-2: product scales of the three gates, row 3: b_hn
     __shared__ float bias_s[3][GRU_H];
     __shared__ float ln_gb[2][GRU_H];                    // LayerNorm weight / bias and the temporal layout's step offsets: no vector-memory load
-    __shared__ int64_t soff_s[32];                       // outside the x pipeline (any wait on one is a wait for the x rows in flight, see below)
+    __shared__ int64_t soff_s[32];                       // steps <= 32 when step_off is set (ctgcn_gru_layer_f32); outside the x pipeline (any wait on one is a wait for the x rows in flight, see below)
     __shared__ int32_t ord_s[4][16];                     // row-plan forms: output rows and step mask of the tiles in flight (ring of four, see below)
     __shared__ mask_t msk_s[4];
     // the row-plan forms have no hrow staging: room for more fragments.  The recompute pass (SAVE) takes two more: with 12 the x prefetch
@@ -4709,6 +4709,8 @@ int ctgcn_gru_layer_f32(int64_t rows, int32_t steps, int32_t d_in, int32_t hidde
                         const int64_t *step_offsets, int64_t ld_row, void *stream)
 {
     if (step_offsets && (ld_row < d_in || (ld_row & 3))) return fail(CTGCN_E_INVALID, "gru_layer: ld_row=%lld must be a multiple of 4 and >= d_in", (long long)ld_row);
+    // the 8-wave kernel stages the offset table in soff_s[32] (LDS): a longer table would be read past its end
+    if (step_offsets && steps > 32) return fail(CTGCN_E_UNSUPPORTED, "gru_layer: step_offsets cover at most 32 steps (got %d)", steps);
     if (hidden != GRU_H || d_in != GRU_H) return fail(CTGCN_E_UNSUPPORTED, "gru_layer: only d_in = hidden = %d is built (got %d, %d)", GRU_H, d_in, hidden);
     if (gates_out && (reduce_sum || ln_weight)) return fail(CTGCN_E_INVALID, "gru_layer: gates_out needs reduce_sum == 0 and no LayerNorm (raw h sequence)");
     if (gates_out && !aligned16(gates_out)) return fail(CTGCN_E_INVALID, "gru_layer: gates_out must be 16-byte aligned");

@@ -754,10 +754,12 @@ def _gru_forward(seq, w_ih, w_hh, bias, b_hn, ln_w, ln_b, eps, reduce_sum, out=N
     return out
 
 
-def gru_steps_scattered_ok(rnn, base):
-    """gru_sequence_scattered covers what the register-resident layer kernel covers: GRU 128 -> 128, fp16x2 arithmetic, 8-wave build"""
+def gru_steps_scattered_ok(rnn, base, steps=None):
+    """gru_sequence_scattered covers what the register-resident layer kernel covers: GRU 128 -> 128, fp16x2 arithmetic, 8-wave build,
+    and at most 32 steps (the kernel keeps the per-step offset table in 32 LDS slots).  steps: the sequence length — pass it; without it
+    the length is not checked here, and ctgcn_gru_layer_f32 refuses a longer table with CTGCN_E_UNSUPPORTED."""
     import os
-    return (gru_fused_ok(rnn, base) and rnn.input_size == rnn.hidden_size and forward_split_mode() == 2 and layer_kernel_enabled(False)
+    return ((steps is None or 1 <= steps <= 32) and gru_fused_ok(rnn, base) and rnn.input_size == rnn.hidden_size and forward_split_mode() == 2 and layer_kernel_enabled(False)
             and os.environ.get("CTGCN_GRU_LAYER_WAVES", "8") != "4" and rnn.weight_ih_l0.is_contiguous()
             and not (torch.is_grad_enabled() and any(p.requires_grad for p in rnn.parameters())))
 

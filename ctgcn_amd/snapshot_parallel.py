@@ -314,7 +314,7 @@ def _forward_sharded_pipelined(model, x_list, adj_list):
     from . import ops
     ev1 = mark()
     ev2 = None
-    if recv.is_cuda and d == 128 and ops.gru_steps_scattered_ok(model.rnn, recv):
+    if recv.is_cuda and d == 128 and ops.gru_steps_scattered_ok(model.rnn, recv, plan.T):
         # the temporal GRU reads the receive buffer in time order through a per-step offset table: no [nodes, T, d] copy at all
         for w in works:
             w.wait()

@@ -247,7 +247,8 @@ int ctgcn_lstm_seq_bwd_f32(int64_t rows, int32_t steps, int32_t hidden, const fl
  * training without the gi round trip.
  * step_offsets (optional, device int64[steps]) + ld_row: x of step t of sequence r is read at x + r ld_row + step_offsets[t] (floats;
  * offsets multiples of 4) instead of x + (r steps + t) ldx - the steps of a sequence may live in different buffers' regions (the temporal
- * GRU of models.py:249 on the receive buffer of a snapshot-parallel exchange, no stack / transpose copy).
+ * GRU of models.py:249 on the receive buffer of a snapshot-parallel exchange, no stack / transpose copy).  At most 32 steps with
+ * step_offsets: longer tables return CTGCN_E_UNSUPPORTED (the caller gathers such sequences into a dense x first).
  */
 int ctgcn_gru_layer_f32(int64_t rows, int32_t steps, int32_t d_in, int32_t hidden, const float *x, int64_t ldx, const float *w_ih,
                         const float *w_hh, const float *bias_gi, const float *b_hn, const float *ln_weight, const float *ln_bias,

@@ -173,7 +173,7 @@ def test_sharded_inference_ctgcn_s_two_ranks(monkeypatch):
     assert all(loop.run(body))
 
 
-@pytest.mark.parametrize("rows,steps,ld_row", [(1000, 5, 128), (257, 16, 384), (33, 3, 128), (4096, 8, 256)])
+@pytest.mark.parametrize("rows,steps,ld_row", [(1000, 5, 128), (257, 16, 384), (33, 3, 128), (4096, 8, 256), (257, 32, 384)])
 def test_gru_sequence_scattered_reads_a_permuted_offset_table(rows, steps, ld_row):
     """ops.gru_sequence_scattered: step t of row r lives at base + step_offsets[t] + r * ld_row floats.  Steps laid out in a permuted order with
     gaps between them (and junk between rows when ld_row > 128) must give exactly the dense call's result."""
@@ -197,8 +197,76 @@ def test_gru_sequence_scattered_reads_a_permuted_offset_table(rows, steps, ld_ro
     step_off = torch.tensor(offs, dtype=torch.int64, device=dev)
     with torch.no_grad():
         assert ops.gru_steps_scattered_ok(rnn, base)
+        assert ops.gru_steps_scattered_ok(rnn, base, steps)
         want = ops.gru_sequence(rnn, x, norm, False)
         got = ops.gru_sequence_scattered(rnn, norm, base, step_off, ld_row, rows)
     assert got.shape == (rows, steps, 128)
     assert torch.isfinite(got).all()
     assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize("steps", [33, 40])
+def test_scattered_gru_refuses_more_than_32_steps(steps):
+    """The layer kernel keeps the step-offset table in 32 LDS slots: a longer table is refused by the host call (CTGCN_E_UNSUPPORTED, nothing
+    launched, the output untouched) and gru_steps_scattered_ok sends such windows to the dense copy."""
+    from ctgcn_amd import _lib, ops
+    from ctgcn_amd._lib import ptr
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    rnn = torch.nn.GRU(128, 128, batch_first=True).to(dev)
+    rows = 40
+    base = torch.zeros(steps * rows * 128, device=dev)
+    step_off = torch.arange(steps, dtype=torch.int64, device=dev) * (rows * 128)
+    with torch.no_grad():
+        assert ops.gru_steps_scattered_ok(rnn, base, 32)
+        assert not ops.gru_steps_scattered_ok(rnn, base, steps)
+        bias, b_hn = ops._gru_bias(rnn, 128)
+        out = torch.full((rows, steps, 128), float("nan"), device=dev)
+        rc = lib.ctgcn_gru_layer_f32(rows, steps, 128, 128, ptr(base), 128, ptr(rnn.weight_ih_l0), ptr(rnn.weight_hh_l0), ptr(bias), ptr(b_hn),
+                                     None, None, 0.0, 0, ptr(out), 0, None, ptr(step_off), 128, torch.cuda.current_stream().cuda_stream)
+        assert rc == -4, rc                                        # CTGCN_E_UNSUPPORTED
+        assert b"32 steps" in lib.ctgcn_last_error()
+        torch.cuda.synchronize()
+        assert torch.isnan(out).all()
+        with pytest.raises(_lib.CtgcnHipError):
+            ops.gru_sequence_scattered(rnn, None, base, step_off, 128, rows)
+
+
+def test_sharded_inference_of_a_40_snapshot_window(monkeypatch):
+    """T = 40 (Enron has 38 snapshots, Math 77): the temporal GRU of a rank's node slice runs over more steps than the offset table holds,
+    so the exchange is gathered into a dense [nodes, T, d] sequence first — and the output is the unsharded forward's, bit for bit."""
+    from _loopback import LoopbackDist
+    from ctgcn_amd import ops, snapshot_parallel as spp
+    dev = torch.device("cuda", 0)
+    n, T, world = 301, 40, 2
+    graphs, adj, model, xs = _window(n, T, dev)
+    model.eval()
+    with torch.no_grad():
+        want = model(xs, adj).clone()
+    loop = LoopbackDist(world)
+    monkeypatch.setattr(spp, "dist", loop)
+    scattered = {"calls": 0}
+    real = ops.gru_sequence_scattered
+
+    def counting(*a, **k):
+        scattered["calls"] += 1
+        return real(*a, **k)
+    monkeypatch.setattr(ops, "gru_sequence_scattered", counting)
+    models = [copy.deepcopy(model) for _ in range(world)]
+    costs = [g.nnz for g in graphs]
+
+    def body(rank):
+        m = models[rank]
+        plan = spp.shard_ctgcn(m, n, costs=costs, group=loop.group.WORLD, exchange="all_to_all", gather_output=False)
+        mine = plan.assignment[rank]
+        lo, hi = plan.node_range(rank)
+        with torch.no_grad():
+            got = m([xs[t] if t in mine else None for t in range(T)], [adj[t] if t in mine else None for t in range(T)])
+        return {"mine": mine, "bitwise": bool(torch.equal(got, want[:, lo:hi])), "range": (lo, hi), "per": plan.per}
+    reps = loop.run(body)
+    assert sorted(t for r in reps for t in r["mine"]) == list(range(T))
+    assert sum(r["range"][1] - r["range"][0] for r in reps) == n
+    for rank, r in enumerate(reps):
+        assert r["bitwise"], (rank, r)
+    assert reps[0]["per"] == T // world and loop.calls["all_to_all_single"] == reps[0]["per"]      # the pipelined exchange, one per slot
+    assert scattered["calls"] == 0
