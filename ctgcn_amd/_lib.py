@@ -14,7 +14,7 @@ ACT_NONE, ACT_SELU = 0, 1
 OP_KCORE = 1
 OP_INGEST = 2
 MAX_SLOTS = 255
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _c = ctypes
 _vp, _i64, _i32, _u32, _int, _sz = _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_uint32, _c.c_int, _c.c_size_t
@@ -106,6 +106,16 @@ SIGNATURES = {
     "ctgcn_lp_hess_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "ctgcn_lp_hess_f32": (_int, [_i64, _i32, _i32, _u32, _i64, _vp, _i64, _vp, _vp, _vp, _c.c_double, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
     "ctgcn_lp_scores_f32": (_int, [_i64, _i32, _i32, _u32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ctgcn_cent_brandes_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "ctgcn_cent_brandes": (_int, [_i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_cent_eigenvector_workspace_bytes": (_sz, [_i64]),
+    "ctgcn_cent_eigenvector": (_int, [_i64, _vp, _vp, _i32, _c.c_double, _vp, _c.POINTER(_i32), _vp, _sz, _vp]),
+    "ctgcn_ridge_gram_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "ctgcn_ridge_gram_f32": (_int, [_i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_ridge_gram_f64": (_int, [_i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_ridge_sse_workspace_bytes": (_sz, [_i32, _i32]),
+    "ctgcn_ridge_sse_f32": (_int, [_i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_ridge_sse_f64": (_int, [_i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

@@ -1,4 +1,9 @@
-"""Evaluation of trained embeddings.  link_prediction: the reference's evaluation/link_prediction.py on the GPU (ctgcn_eval.hip)."""
+"""Evaluation of trained embeddings.  link_prediction: the reference's evaluation/link_prediction.py on the GPU (ctgcn_eval.hip);
+centrality_prediction: its evaluation/centrality_prediction.py (ctgcn_cent.hip)."""
 from .link_prediction import (DataGenerator, LinkPredictor, aggregate_results, evaluate, evaluate_window,  # noqa: F401
                               link_prediction, make_splits)
 from ._logreg import FitReport, roc_auc  # noqa: F401
+from .centrality_prediction import (CentralityPredictor, PowerIterationFailedConvergence, centralities,  # noqa: F401
+                                    centrality_prediction, ridge_cv_errors)
+from .centrality_prediction import DataGenerator as CentralityDataGenerator  # noqa: F401
+from .centrality_prediction import evaluate as evaluate_centrality  # noqa: F401

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CTGCN_ABI_VERSION 30
+#define CTGCN_ABI_VERSION 31
 
 enum {
     CTGCN_OK = 0,
@@ -649,6 +649,47 @@ int ctgcn_lp_hess_f32(int64_t n, int32_t d, int32_t models, uint32_t measures, i
                       double *hess_out, void *workspace, size_t workspace_bytes, void *stream);
 int ctgcn_lp_scores_f32(int64_t n, int32_t d, int32_t models, uint32_t measures, int64_t n_nodes, const float *E, int64_t lde,
                         const int64_t *src, const int64_t *dst, const float *W, float *score_out, void *stream);
+
+/*
+ * Centrality-prediction evaluation (evaluation/centrality_prediction.py; ctgcn_amd/evaluation/), ctgcn_cent.hip (ABI 31).
+ * row_ptr / col: a symmetric int32 CSR without self loops, n vertices (n <= 2^31 - 1); all centralities are unweighted.
+ *
+ * ctgcn_cent_brandes: one BFS per source s in [s0, s1).  bc_out[v] (double[n]) = Σ_{s in range, s != v} δ_s(v), Brandes' dependency
+ *   sums, UNSCALED (networkx's normalized undirected betweenness is bc · 1/((n-1)(n-2)) over all sources); r_out[s - s0] = vertices
+ *   reached from s (s included), D_out[s - s0] = the sum of their distances (int64[s1 - s0]), the closeness counts.  Path counts and
+ *   dependencies are fp64; sigma and delta are pulled over CSR rows in CSR order and per-block partials of bc are summed in a fixed
+ *   order: repeated calls are bit-identical.  workspace: ctgcn_cent_brandes_workspace_bytes (a state slab per block, at most 2 GiB
+ *   unless one slab is larger).
+ * ctgcn_cent_eigenvector: networkx's eigenvector_centrality iteration: x = 1/n, then up to max_iter steps x <- (A+I)x / ||(A+I)x||_2
+ *   (a zero norm counts as 1), stopping after the first step with Σ|x - x_last| < n·tol.  All steps are enqueued at once; after the
+ *   stop test passes a device flag turns the rest into no-ops.  x_out (double[n]) holds x; *stop_step (host) = the stop step
+ *   (1-based), or 0 when no step passed the test.  One host read: the call synchronises `stream`.
+ *   workspace: ctgcn_cent_eigenvector_workspace_bytes.
+ * ctgcn_ridge_gram_{f32,f64}: the k-fold (KFold(folds), unshuffled: contiguous folds, the first n % folds one row longer) augmented
+ *   Grams gram_out[f] = Zᵀ_f [X 1 Y]_f restricted to the rows of Z = [X 1] (double[folds, d+1, d+1+targets]), X row r at X + r*ldx,
+ *   Y double[n, targets].  fp64 accumulation, per-chunk partials summed in a fixed order.  d <= 512 and targets <= 8, else
+ *   CTGCN_E_UNSUPPORTED.  workspace: ctgcn_ridge_gram_workspace_bytes.
+ * ctgcn_ridge_sse_{f32,f64}: sse_out[f, p] = Σ_{r in fold f} (Y[r, target_of[p]] - X[r]·W[f, p, :d] - W[f, p, d])² for models
+ *   p < models <= 64, W double[folds, models, d+1], target_of int32[models] (device).  workspace: ctgcn_ridge_sse_workspace_bytes.
+ */
+size_t ctgcn_cent_brandes_workspace_bytes(int64_t n, int64_t s0, int64_t s1);
+int ctgcn_cent_brandes(int64_t n, const int32_t *row_ptr, const int32_t *col, int64_t s0, int64_t s1, double *bc_out,
+                       int64_t *r_out, int64_t *D_out, void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_cent_eigenvector_workspace_bytes(int64_t n);
+int ctgcn_cent_eigenvector(int64_t n, const int32_t *row_ptr, const int32_t *col, int32_t max_iter, double tol, double *x_out,
+                           int32_t *stop_step, void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_ridge_gram_workspace_bytes(int32_t d, int32_t targets, int32_t folds);
+int ctgcn_ridge_gram_f32(int64_t n, int32_t d, int32_t targets, int32_t folds, const float *X, int64_t ldx, const double *Y,
+                         double *gram_out, void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_ridge_gram_f64(int64_t n, int32_t d, int32_t targets, int32_t folds, const double *X, int64_t ldx, const double *Y,
+                         double *gram_out, void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_ridge_sse_workspace_bytes(int32_t models, int32_t folds);
+int ctgcn_ridge_sse_f32(int64_t n, int32_t d, int32_t targets, int32_t folds, int32_t models, const float *X, int64_t ldx,
+                        const double *Y, const double *W, const int32_t *target_of, double *sse_out, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int ctgcn_ridge_sse_f64(int64_t n, int32_t d, int32_t targets, int32_t folds, int32_t models, const double *X, int64_t ldx,
+                        const double *Y, const double *W, const int32_t *target_of, double *sse_out, void *workspace,
+                        size_t workspace_bytes, void *stream);
 
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
