@@ -13,23 +13,29 @@ workload = default `synthetic-1m` = BASELINE config 5 (1M nodes x 16 cumulative 
 `python bench.py --gpus N` with N > 1 and no launcher environment re-launches itself under torch.distributed.run
 (one process per GPU, RCCL, 127.0.0.1 rendezvous); under a launcher (RANK/WORLD_SIZE set) it runs as that rank.
 
-Output (round 6).  stdout carries ONE compact JSON line, < 4 KB (bench.MAX_LINE_BYTES; the driver keeps ~9 KB of stdout — round 5's
+Output.  stdout carries ONE compact JSON line, < 4 KB (bench.MAX_LINE_BYTES; the driver keeps ~9 KB of stdout — round 5's
 23 KB line reached it truncated and unparsed): the contract's keys, `config` {workload, name, nodes, snapshots, max_core,
-aggregated_edges_per_step, parallelism}, `roofline`, `cpu_baseline`, `also` (one-number summaries of the short legs) and `detail_file`.
-The FULL record — everything below — goes to gpurun_out/bench_detail.json (--detail-file), per workload bench_detail_<name>.json.
+aggregated_edges_per_step, parallelism}, `roofline`, `cpu_baseline`, `also` (one-number summaries of the legs) and `detail_file`.
+
+A plain run does only what the headline needs: set-up, what has always come before the timed steps (one second of device copies, whose
+rate goes into `also`, and the pre-warm, --prewarm-s), the W warm-up and N timed steps, --dump-outputs and the line; on windows of
+<= 200 000 nodes also the same forward replayed from one hipGraph, since the headline is the faster of the two.  Its `roofline`,
+`cpu_baseline` and `detail_file` are null, and it writes no detail file unless --detail-file names one.
+--full adds every other leg below, fills those fields and writes the FULL record (--detail-file; by default bench_detail.json, per workload
+bench_detail_<name>.json, in the output folder of the repository root).  The timed steps are the same with and without --full.
   roofline            dominant kernel (the aggregation): algorithmic bytes per launch / HIP-event duration on the launch stream; under the
                       row plan the algorithmic bytes are those of the rows actually written, frac_8d keeps SURVEY §8d's formula;
                       `traffic` = HBM bytes per launch measured BY THIS RUN: two `rocprofv3 --pmc` passes (FETCH_SIZE, WRITE_SIZE apart, the
                       gfx950 x2 correction of MI355X_MICROARCH.md) over a 2-step run of this script (pmc_traffic; --no-pmc: null)
   cpu_baseline        the reference's torch.sparse.mm loop on the host cores (uncoalesced COO as the reference builds it + a coalesced-CSR
-                      variant), a bounded sample (--cpu-budget-s, default 30 s: one pass of the full 8-matrix loop of the largest
-                      snapshot each; --full: 100 s = median of three), rank 0, N=1 only
+                      variant), a bounded sample (--cpu-budget-s, default 100 s: the median of three passes of the full 8-matrix loop of
+                      the largest snapshot where they fit, one pass each otherwise), rank 0, N=1 only
   (detail file only)  roofline_by_width, roofline_gru (matrix-core kernels), roofline_kcore, exact_fp32 (CTGCN_FP32_MFMA_ONLY=1),
-                      training_step (+ backward rooflines), hbm_copy_GBps_measured, configs (BASELINE configs 2-4: short runs of this
-                      script), hipgraph (small windows: the same forward replayed from one hipGraph, frozen and live weights), pmc;
-                      --full adds torch_rocm_baseline (the reference's own GPU path, stock PyTorch-ROCm), the reference-loss training
-                      batch, per-config baselines and the forced single-rank RCCL leg
-The default run (the driver's command) takes ~100 s on an MI355X box; --full several minutes.
+                      training_step (+ backward rooflines, the reference-loss training batch), hbm_copy_GBps_measured, configs (BASELINE
+                      configs 2-4: short --full runs of this script, with their own baselines), hipgraph (small windows: the same forward
+                      replayed from one hipGraph, frozen and live weights), pmc, torch_rocm_baseline (the reference's own GPU path, stock
+                      PyTorch-ROCm) and forced_dist (the forced single-rank RCCL leg)
+A plain run of config 5 spends ~10 s outside its steps on an MI355X box (the graphs, the copy pass, the pre-warm); --full several minutes.
 
 --dump-outputs DIR writes what the last timed step returned (dump_outputs): graphs, features and weights are seeded, so two builds run
 with the same arguments can be compared output for output.
@@ -90,29 +96,28 @@ def parse():
                     help="launcher / rendezvous / per-rank bookkeeping only, on the CPU with the gloo backend and no kernels (the `not gpu` test of "
                          "the multi-rank path of this script: self-launch, assignment, stats gather, barriers, max-over-ranks timing, one JSON line)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the host-core baseline and the stock-PyTorch-on-this-GPU baseline")
-    ap.add_argument("--train-leg", action="store_true", help="run the training-step leg even with --no-extras (the per-config runs of the default line)")
+    ap.add_argument("--train-leg", action="store_true", help="run the training-step leg even with --no-extras (the per-config runs of --full)")
     ap.add_argument("--no-extras", action="store_true", help="skip the exact-fp32 forward and the k-core roofline legs")
-    ap.add_argument("--cpu-budget-s", type=float, default=30.0,
-                    help="seconds of host time for the CPU baseline (SURVEY 8d: a bounded sample, 10-30 s; config 5: one pass of the full 8-matrix loop "
-                         "as COO + one as CSR; --full: 100 s = three passes each)")
+    ap.add_argument("--cpu-budget-s", type=float, default=100.0,
+                    help="seconds of host time for the CPU baseline (SURVEY 8d: a bounded sample; three passes of each operand format where "
+                         "they fit; config 5: one pass of the full 8-matrix loop as COO + one as CSR)")
     ap.add_argument("--full", action="store_true",
-                    help="everything the detail file can hold: stock-PyTorch-on-this-GPU baseline, reference-loss training batch, per-config "
-                         "training steps and baselines, forced single-rank RCCL leg (minutes; the default run keeps to the headline, its roofline "
-                         "and CPU baseline plus short legs)")
+                    help="every leg besides the headline: rooflines and kernel times, exact-fp32 forward, k-core, "
+                         "training step, CPU and stock-PyTorch baselines, PMC traffic, BASELINE configs 2-4, forced single-rank RCCL leg, and the "
+                         "detail file (minutes; a plain run keeps to set-up, warm-up, the timed steps and the line).  --no-cpu-baseline, "
+                         "--train-leg, --no-extras, --cpu-budget-s and --no-pmc shape these legs")
     ap.add_argument("--no-pmc", action="store_true",
                     help="do not measure roofline.traffic (two `rocprofv3 --pmc` passes of a 2-step run of this script, FETCH_SIZE and WRITE_SIZE apart)")
     ap.add_argument("--prewarm-s", type=float, default=1.0, help="seconds of untimed stepping before the warm-up steps (clocks)")
     ap.add_argument("--detail-file", default=None,
-                    help="where the full record goes (default gpurun_out/bench_detail.json, per workload: bench_detail_<name>.json); stdout "
-                         "carries ONE compact JSON line (< 4 KB)")
+                    help="where the full record goes (--full: by default bench_detail.json, per workload bench_detail_<name>.json, in the output "
+                         "folder of the repository root; a plain run writes it only when named here); stdout carries ONE compact JSON line (< 4 KB)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; at most 64 MB in all: "
                          "beyond that a fixed seeded sample of node rows, listed in DIR/<name>__index.npy)")
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
-    if a.full and a.cpu_budget_s == 30.0:
-        a.cpu_budget_s = 100.0
     return a
 
 
@@ -369,6 +374,8 @@ def main():
             elapsed = float(tt.item())
         return 1000.0 * elapsed / steps, res
 
+    # in every run, --full or not: the timed steps have always followed this second of copies, and without it config 5 measured ~1 % faster
+    # on the same box (149.8 against 151.4 ms, two runs each), so it stays part of what comes before them
     copy_bw = measure_copy_bandwidth(dev) if rank == 0 else None
     ms_per_step, res = timed(args.steps, args.warmup, prewarm_s=args.prewarm_s)
     out = first(res)
@@ -382,17 +389,19 @@ def main():
         dump_outputs(args.dump_outputs, arrays, DUMP_BYTES // world, log)
     del res
     per_rank_ms = None
-    if use_dist:
+    if use_dist and args.full:
         # DESIGN §5's model, line by line: every rank's compute / exposed exchange / temporal head over the timed steps
         mine_ms = spp.shard_phase_ms(model, last=args.steps) or {}
         mine_ms.update(rank=rank, snapshots=mine, aggregated_edges=layers * sum(stats[t]["agg"] for t in mine))
         per_rank_ms = [None] * world
         dist.all_gather_object(per_rank_ms, mine_ms)
         model.shard_timing = None
-    recorded = list(launches)
+    # the launch timer (and model.shard_timing) stay on in the timed steps of every run, so that they are the same steps with and without
+    # --full; a plain run reads none of those events: the roofline objects below stay empty
+    recorded = list(launches) if args.full else []
     roof_steps = args.steps
     roof_pass = "the timed steps"
-    if not use_dist and not args.train and not args.graph and n <= 200_000 and os.environ.get("CTGCN_STREAMS", "") != "1":
+    if args.full and not use_dist and not args.train and not args.graph and n <= 200_000 and os.environ.get("CTGCN_STREAMS", "") != "1":
         # small graphs run their snapshot branches on several streams: kernels overlap, and an event pair around one launch then
         # also times its neighbours.  Per-kernel durations for the roofline objects come from a separate single-stream pass.
         os.environ["CTGCN_STREAMS"] = "1"
@@ -421,11 +430,12 @@ def main():
             graph_info = {"replay_ms_per_step": round(g_ms, 4), "eager_ms_per_step": round(ms_per_step, 4), "capture_s": round(cap_s, 2),
                           "bit_identical_to_eager": True, "mode": "frozen_weights=True: cached operand forms of the weights recorded; re-capture after an update"}
             del g_runner, g_out
-            g_runner = GraphedInference(model, x_list, adj_list)
-            g2_ms, g_out = timed(args.steps, args.warmup, step=lambda: first(g_runner()))
-            assert torch.equal(g_out, out), "hipGraph replay differs from the eager forward"
-            graph_info["replay_ms_per_step_live_weights"] = round(g2_ms, 4)
-            del g_runner, g_out
+            if args.full:
+                g_runner = GraphedInference(model, x_list, adj_list)
+                g2_ms, g_out = timed(args.steps, args.warmup, step=lambda: first(g_runner()))
+                assert torch.equal(g_out, out), "hipGraph replay differs from the eager forward"
+                graph_info["replay_ms_per_step_live_weights"] = round(g2_ms, 4)
+                del g_runner, g_out
             # headline = the faster of the two ways to run the SAME forward (same kernels, same bits); both are on the record
             if g_ms < ms_per_step:
                 eager_ms, ms_per_step = ms_per_step, g_ms
@@ -587,7 +597,7 @@ def main():
     # ------------------------------------------------------------------------- extras: exact fp32 forward, k-core peel
     exact = None
     roof_kcore = None
-    if not args.no_extras and not args.train and not args.graph:
+    if args.full and not args.no_extras and not args.train and not args.graph:
         prev = os.environ.get("CTGCN_FP32_MFMA_ONLY")
         os.environ["CTGCN_FP32_MFMA_ONLY"] = "1"
         try:
@@ -639,9 +649,10 @@ def main():
         torch.cuda.empty_cache()
     # ------------------------------------------------------------------------- training step (fwd AND fwd+bwd)
     train = None
-    if (not args.no_extras or args.train_leg) and not args.train and not args.graph and not use_dist and os.environ.get("CTGCN_BENCH_TRAIN_LEG", "1") != "0":
+    if args.full and (not args.no_extras or args.train_leg) and not args.train and not args.graph and not use_dist and \
+            os.environ.get("CTGCN_BENCH_TRAIN_LEG", "1") != "0":
         try:
-            train = training_leg(model, x_list, adj_list, ops, first, agg_edges_step, log, reference_loss=args.full)
+            train = training_leg(model, x_list, adj_list, ops, first, agg_edges_step, log)
         except Exception as exc:          # e.g. out of memory on a box that is not empty: the forward line above must still be printed
             train = {"error": "%s: %s" % (type(exc).__name__, str(exc)[:400])}
             log("training leg failed: %s" % train["error"])
@@ -654,7 +665,7 @@ def main():
 
     # ------------------------------------------------------------------------------------- CPU baselines (N=1)
     cpu = cpu_k = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         widths = [hid if W["model"] == "C" else emb] + [emb] * (layers - 1)
         cpu = cpu_baseline(adj_list, widths, args.cpu_budget_s, log)
         cpu_k = cpu_baseline_kcore(kc_graph, n, log) if kc_graph is not None else None
@@ -727,29 +738,31 @@ def main():
     del model, x_list, adj_list, out
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
-    if world == 1 and not use_dist and not args.no_pmc and not args.train and not args.graph and roof is not None:
+    if world == 1 and args.full and not use_dist and not args.no_pmc and not args.train and not args.graph and roof is not None:
         line["pmc"] = pmc_traffic(args, roof, log)
         if line["pmc"].get("hbm_bytes_per_launch") is not None:
             roof["traffic"] = line["pmc"]["hbm_bytes_per_launch"]
             roof["traffic_over_algorithmic_bytes"] = round(roof["traffic"] / float(roof["algorithmic_bytes_per_launch"]), 4)
     # the other BASELINE configs (2, 3, 4 math / AS) in the SAME driver run: short runs of this script, one after the other, on the same GPU
     line["configs"] = None
-    if headline and not args.no_extras and os.environ.get("CTGCN_BENCH_OTHER_CONFIGS", "1") != "0":
+    if headline and args.full and not args.no_extras and os.environ.get("CTGCN_BENCH_OTHER_CONFIGS", "1") != "0":
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
-        line["configs"] = other_configs(line, log, args.full)
-        if args.full:
-            line["forced_dist"] = forced_dist_leg(args, log)
+        line["configs"] = other_configs(line, log)
+        line["forced_dist"] = forced_dist_leg(args, log)
     line["bench_wall_s"] = round(time.time() - T_START, 1)
     detail_path = args.detail_file or os.path.join(ROOT, "gpurun_out", "bench_detail%s.json" % ("" if args.workload == "synthetic-1m" else "_" + args.workload))
-    try:
-        os.makedirs(os.path.dirname(detail_path) or ".", exist_ok=True)
-        with open(detail_path, "w") as fh:
-            json.dump(line, fh, indent=1)
-        log("full record: %s (%d bytes)" % (detail_path, os.path.getsize(detail_path)))
-    except OSError as exc:
-        log("could not write %s: %s" % (detail_path, exc))
-        detail_path = None
+    if not args.full and args.detail_file is None:
+        detail_path = None                     # a plain run keeps to its one line
+    else:
+        try:
+            os.makedirs(os.path.dirname(detail_path) or ".", exist_ok=True)
+            with open(detail_path, "w") as fh:
+                json.dump(line, fh, indent=1)
+            log("full record: %s (%d bytes)" % (detail_path, os.path.getsize(detail_path)))
+        except OSError as exc:
+            log("could not write %s: %s" % (detail_path, exc))
+            detail_path = None
     record = compact_record(line, detail_path)
     text = json.dumps(record, separators=(",", ":"))
     assert len(text) < MAX_LINE_BYTES, "bench line is %d bytes (limit %d): move fields to the detail file" % (len(text), MAX_LINE_BYTES)
@@ -872,13 +885,13 @@ def pmc_traffic(args, roof, log):
     if exe is None:
         return {"error": "rocprofv3 not found"}
     kern = roof["kernel"].split(" ")[0].split("<")[0]
-    res = {"kernel": kern, "command": "rocprofv3 --kernel-trace --pmc <C> -- python bench.py --workload %s --steps 1 --warmup 1 --prewarm-s 0 --no-cpu-baseline "
-                                      "--no-extras --no-pmc (C = FETCH_SIZE, then WRITE_SIZE)" % args.workload}
+    res = {"kernel": kern, "command": "rocprofv3 --kernel-trace --pmc <C> -- python bench.py --workload %s --steps 1 --warmup 1 --prewarm-s 0 --full "
+                                      "--no-cpu-baseline --no-extras --no-pmc (C = FETCH_SIZE, then WRITE_SIZE)" % args.workload}
     t0 = time.time()
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         tmp = tempfile.mkdtemp(prefix="ctgcn_pmc_", dir="/tmp")
         cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", tmp, "-o", "bench", "--", sys.executable, os.path.abspath(__file__),
-               "--workload", args.workload, "--steps", "1", "--warmup", "1", "--prewarm-s", "0", "--no-cpu-baseline", "--no-extras", "--no-pmc",
+               "--workload", args.workload, "--steps", "1", "--warmup", "1", "--prewarm-s", "0", "--full", "--no-cpu-baseline", "--no-extras", "--no-pmc",
                "--detail-file", os.path.join(tmp, "detail.json")]
         try:
             p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=240, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"))
@@ -986,13 +999,14 @@ def config_summary(line):
             "cpu_baseline": {k: cpu.get(k) for k in ("value", "unit", "cores", "kind", "value_coalesced_csr", "protocol")} if cpu else None}
 
 
-def other_configs(main_line, log, full=False):
-    """{name: summary} for BASELINE configs 2-4 (+ this run's config 5): `python bench.py --workload W --steps 20 --no-extras` each, ~10 s."""
+def other_configs(main_line, log):
+    """{name: summary} for BASELINE configs 2-4 (+ this run's config 5): `python bench.py --workload W --steps 20 --full --no-extras --train-leg`
+    each (with a 4 s CPU baseline and the stock-PyTorch baseline)."""
     out = {"synthetic-1m": config_summary(main_line)}
     for w in ("enron-like", "facebook-like", "math-like", "as-like"):
         detail = os.path.join(ROOT, "gpurun_out", "bench_detail_%s.json" % w)
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--steps", "20", "--warmup", "3", "--no-extras", "--train-leg", "--no-pmc",
-               "--detail-file", detail] + (["--full", "--cpu-budget-s", "4"] if full else ["--no-cpu-baseline"])
+               "--detail-file", detail, "--full", "--cpu-budget-s", "4"]
         t0 = time.time()
         try:
             if os.path.exists(detail):
@@ -1014,7 +1028,7 @@ def forced_dist_leg(args, log):
     can be checked against the headline (what is left is RCCL's send -> recv copy of 8 GB that a single rank does for nothing)."""
     detail = os.path.join(ROOT, "gpurun_out", "bench_detail_forced_dist.json")
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--no-extras", "--no-cpu-baseline", "--no-pmc", "--detail-file", detail]
+           "--full", "--no-extras", "--no-cpu-baseline", "--no-pmc", "--detail-file", detail]
     env = dict(os.environ, CTGCN_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     t0 = time.time()
@@ -1031,7 +1045,7 @@ def forced_dist_leg(args, log):
     return out
 
 
-def training_leg(model, x_list, adj_list, ops, first, agg_edges_step, log, reference_loss=True):
+def training_leg(model, x_list, adj_list, ops, first, agg_edges_step, log):
     """fwd + bwd + Adam on the same window (the reference's training step, embedding.py:346-352, with the surrogate loss
     out.square().mean(): the negative-sampling loss is outside the hot path):
     2 warm-up + 3 timed steps after the forward measurement,
@@ -1126,7 +1140,7 @@ def training_leg(model, x_list, adj_list, ops, first, agg_edges_step, log, refer
             lambda m: rs(m) * m["fresh"] * (1536.0 + 516.0 + 512.0),
             lambda m: rs(m) * m["fresh"] * 2.0 * 128 * 384 * (3 + 4))
         log("training step: %.1f ms" % ms)
-        if reference_loss and os.environ.get("CTGCN_BENCH_REFERENCE_LOSS", "1") != "0":
+        if os.environ.get("CTGCN_BENCH_REFERENCE_LOSS", "1") != "0":
             try:
                 res["reference_loss_batch_step"] = reference_loss_leg(model, x_list, adj_list, first, opt, log)
             except Exception as exc:

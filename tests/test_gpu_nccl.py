@@ -50,7 +50,8 @@ def test_bench_single_rank_sharded_path_matches_plain(tmp_path):
         env = dict(os.environ, CTGCN_FORCE_DIST=force, MASTER_PORT=str(_free_port()))
         detail = str(tmp_path / ("detail%s.json" % force))
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
-                              "--no-cpu-baseline", "--no-extras", "--no-pmc", "--detail-file", detail], env=env, capture_output=True, text=True, timeout=600)
+                              "--full", "--no-cpu-baseline", "--no-extras", "--no-pmc", "--detail-file", detail], env=env, capture_output=True, text=True,
+                             timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         json_lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
         assert len(json_lines) == 1 and out.stdout.strip().splitlines()[-1] == json_lines[0], out.stdout[-500:]   # ONE line, and it is the last

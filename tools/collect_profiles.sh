@@ -8,10 +8,10 @@ OUT=$PWD/gpurun_out/${1:-r6p}
 mkdir -p $OUT
 REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-pmc --detail-file $OUT/detail_under_rocprof.json"
+B="python $REPO/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras --no-pmc --detail-file $OUT/detail_under_rocprof.json"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- $B > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 for w in enron-like facebook-like math-like as-like; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$w -o bench -- python $REPO/bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-pmc --detail-file $OUT/detail_$w.json > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$w -o bench -- python $REPO/bench.py --workload $w --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras --no-pmc --detail-file $OUT/detail_$w.json > $OUT/bench_$w.json 2> $OUT/bench_$w.err
 done
 cd $REPO
 for d in stats stats_enron-like stats_facebook-like stats_math-like stats_as-like; do
