@@ -116,6 +116,16 @@ SIGNATURES = {
     "ctgcn_ridge_sse_workspace_bytes": (_sz, [_i32, _i32]),
     "ctgcn_ridge_sse_f32": (_int, [_i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ctgcn_ridge_sse_f64": (_int, [_i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_nc_chunks": (_i64, [_i64]),
+    "ctgcn_nc_hess_parts": (_i64, [_i64, _i64]),
+    "ctgcn_nc_grad_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "ctgcn_nc_grad_f32": (_int, [_i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                 _sz, _vp]),
+    "ctgcn_nc_hess_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "ctgcn_nc_hess_f32": (_int, [_i32, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                                 _sz, _vp]),
+    "ctgcn_nc_predict_f32": (_int, [_i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                                    _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

@@ -1,5 +1,6 @@
 """Evaluation of trained embeddings.  link_prediction: the reference's evaluation/link_prediction.py on the GPU (ctgcn_eval.hip);
-centrality_prediction: its evaluation/centrality_prediction.py (ctgcn_cent.hip)."""
+centrality_prediction: its evaluation/centrality_prediction.py (ctgcn_cent.hip); node_classification: its
+evaluation/node_classification.py (ctgcn_nodecls.hip)."""
 from .link_prediction import (DataGenerator, LinkPredictor, aggregate_results, evaluate, evaluate_window,  # noqa: F401
                               link_prediction, make_splits)
 from ._logreg import FitReport, roc_auc  # noqa: F401
@@ -7,3 +8,8 @@ from .centrality_prediction import (CentralityPredictor, PowerIterationFailedCon
                                     centrality_prediction, ridge_cv_errors)
 from .centrality_prediction import DataGenerator as CentralityDataGenerator  # noqa: F401
 from .centrality_prediction import evaluate as evaluate_centrality  # noqa: F401
+from .node_classification import (NodeClassifier, evaluate_window as evaluate_node_classification_window,  # noqa: F401
+                                  node_classification)
+from .node_classification import DataGenerator as NodeClsDataGenerator  # noqa: F401
+from .node_classification import aggregate_results as aggregate_node_classification_results  # noqa: F401
+from .node_classification import evaluate as evaluate_node_classification  # noqa: F401

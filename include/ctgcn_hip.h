@@ -691,6 +691,54 @@ int ctgcn_ridge_sse_f64(int64_t n, int32_t d, int32_t targets, int32_t folds, in
                         const double *Y, const double *W, const int32_t *target_of, double *sse_out, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/*
+ * Node-classification evaluation (evaluation/node_classification.py; ctgcn_amd/evaluation/), ctgcn_nodecls.hip.
+ * A launch covers `problems` independent one-vs-rest problems described by a problem table (all arrays on the device):
+ *   - problem p owns the entries [row_start[p], row_start[p+1]) of rows (int64: a row of E, row v at E + v*lde, 1 <= d <= 256; rows
+ *     outside [0, n_emb) read as zero) and y (int32: the entry's class index in [0, K_p));
+ *   - problem p owns the models [model_start[p], model_start[p+1]) (int32).  The model arrays are indexed by m - model_start[0]:
+ *     model_pos (int32: the positive class), model_w (double[models, 2]: balanced weights of the negative and positive rows),
+ *     model_flag (int32: 0 fitted, 1 constant probability 0, 2 constant probability 1), the parameters W and the outputs;
+ *   - chunk_start / part_start (int64[problems+1]): the blocks of problem p; the pass entry points need ctgcn_nc_chunks(n_p) blocks
+ *     for a problem of n_p rows, the Hessian ctgcn_nc_hess_parts(n_p, hess_max).  total_chunks / total_parts = the last entry.
+ *   - max_models >= the largest model count of a problem.  models = model_start[problems] - model_start[0].
+ * Model m has z = w·x + b with (w, b) = W[m*(d+1) .. +d].  ctgcn_nc_grad_f32 and ctgcn_nc_predict_f32 take W as float[2, models, d+1]:
+ * hi then lo parts (hi + lo = the fp64 parameters; lo may be zero); ctgcn_nc_hess_f32 takes float[models, d+1].  Each block gathers a
+ * 32-row tile of its problem into LDS once for up to 64 models (32 when d > 131).  Per-block partials are summed per problem in block
+ * order and the block count of a problem depends on its row count alone: a problem's outputs are bit-identical across calls and
+ * whichever problems share the launch.
+ *
+ * ctgcn_nc_grad_f32: loss_out[m] = Σ_i s_i softplus(∓z_i) (double[models]) and grad_out[m*(d+1) + j] = Σ_i s_i (σ(z_i) - y_i) x̃_ij,
+ *   x̃ = (x, 1) (double[models, d+1]), y_i = (y == model_pos[m]), s_i its balanced weight; zero for flagged models.  fp32 within a
+ *   32-row tile, fp64 across tiles.  workspace: ctgcn_nc_grad_workspace_bytes.
+ * ctgcn_nc_hess_f32: hess_out[m] = Σ_i s_i σ(1-σ) x̃_i x̃_iᵀ (double[models, d+1, d+1], symmetric) over the subsample i = 0, k, 2k, ...
+ *   of each problem, k = ceil(n_p / hess_max) (every row when n_p <= hess_max), with the full set's weights; zero for flagged models.
+ *   fp32 over parts of at most 1024 subsample rows, fp64 across parts.  workspace: ctgcn_nc_hess_workspace_bytes.
+ * ctgcn_nc_predict_f32: problem p holds `groups` C groups of models, group-major: K_p = n_classes[p] models per group (classes
+ *   0..K_p-1), or one model (class 1) when K_p = 2.  For every entry and group: pred_out[(entry - row_start[0])*groups + g] (int32) =
+ *   the first argmax over the group's models of fp64 expit(z) (a flagged model contributes its constant; K_p = 2: class 1 iff
+ *   p > 1 - p), and correct_out[p*groups + g] (int64) = the entries whose prediction equals y.  max_classes >= every K_p, at most
+ *   64 (32 when d > 131), else CTGCN_E_UNSUPPORTED.
+ */
+int64_t ctgcn_nc_chunks(int64_t n);
+int64_t ctgcn_nc_hess_parts(int64_t n, int64_t hess_max);
+size_t ctgcn_nc_grad_workspace_bytes(int64_t total_chunks, int32_t d, int32_t max_models);
+int ctgcn_nc_grad_f32(int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *chunk_start,
+                      int64_t total_chunks, const int64_t *rows, const int32_t *y, const int32_t *model_start, const int32_t *model_pos,
+                      const double *model_w, const int32_t *model_flag, int64_t n_emb, const float *E, int64_t lde, const float *W,
+                      int64_t models, double *loss_out, double *grad_out, void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_nc_hess_workspace_bytes(int64_t total_parts, int32_t d, int32_t max_models);
+int ctgcn_nc_hess_f32(int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *part_start,
+                      int64_t total_parts, int64_t hess_max, const int64_t *rows, const int32_t *y, const int32_t *model_start,
+                      const int32_t *model_pos, const double *model_w, const int32_t *model_flag, int64_t n_emb, const float *E,
+                      int64_t lde, const float *W, int64_t models, double *hess_out, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int ctgcn_nc_predict_f32(int32_t problems, int32_t d, int32_t max_classes, int32_t groups, const int64_t *row_start,
+                         const int64_t *chunk_start, int64_t total_chunks, const int64_t *rows, const int32_t *y,
+                         const int32_t *n_classes, const int32_t *model_start, const int32_t *model_flag, int64_t n_emb,
+                         const float *E, int64_t lde, const float *W, int64_t models, int32_t *pred_out, int64_t *correct_out,
+                         void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
