@@ -126,6 +126,18 @@ SIGNATURES = {
                                  _sz, _vp]),
     "ctgcn_nc_predict_f32": (_int, [_i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
                                     _vp]),
+    "ctgcn_sim_panel_cols": (_i64, [_i64, _i64]),
+    "ctgcn_sim_series_workspace_bytes": (_sz, [_i64, _i64]),
+    "ctgcn_sim_series": (_int, [_i64, _vp, _vp, _vp, _c.c_double, _i32, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "ctgcn_sim_finish_workspace_bytes": (_sz, [_i64]),
+    "ctgcn_sim_finish": (_int, [_i64, _i32, _c.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_sim_coo": (_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctgcn_sim_gram_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "ctgcn_sim_gram_f64": (_int, [_i64, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "ctgcn_sim_normalize_workspace_bytes": (_sz, [_i64]),
+    "ctgcn_sim_normalize": (_int, [_i64, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_sim_spearman_workspace_bytes": (_sz, [_i64]),
+    "ctgcn_sim_spearman": (_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

@@ -739,6 +739,50 @@ int ctgcn_nc_predict_f32(int32_t problems, int32_t d, int32_t max_classes, int32
                          const float *E, int64_t lde, const float *W, int64_t models, int32_t *pred_out, int64_t *correct_out,
                          void *stream);
 
+/*
+ * Similarity-prediction evaluation (evaluation/similarity_prediction.py; ctgcn_amd/evaluation/), ctgcn_sim.hip.
+ * The block: m vertices (the graph's non-isolated ones under a monotone relabel), row_ptr / col int32 and val double a symmetric
+ * CSR with sorted columns, S double[m, m] row-major.
+ *
+ * ctgcn_sim_series: the columns [col0, col1) of S_iter_num, where S_1 = I and S_k = c·A·S_(k-1) + I (Leicht, Holme and Newman;
+ *   the reference's dsd).  Every entry is the fp64 sum over its CSR row in CSR order, acc = acc + a_ij·x_j from +0.0, never fused,
+ *   then c·acc + δ_ij: the reference's scipy product bit for bit.  The columns are walked in panels of `panel` (every step of a
+ *   panel before the next one; one launch per step and panel); the result does not depend on `panel`.  iter_num >= 1.
+ *   workspace: ctgcn_sim_series_workspace_bytes (two m x panel buffers).  ctgcn_sim_panel_cols: the default panel, the widest whose
+ *   buffers and A stay inside the Infinity Cache.
+ * ctgcn_sim_finish: in place, S <- (S + Sᵀ)/2 - I, then S <- (S - mn)/(mx - mn) with entries below eps set to 0, where mn, mx are
+ *   the block's minimum and maximum, taken with 0 as well when pad_zero (the zero rows and columns of isolated vertices).
+ *   stats_out (device double[2]) = mn, mx; row_nnz (device int64[m]) = the non-zeros left per row (NaN counts).
+ *   workspace: ctgcn_sim_finish_workspace_bytes.
+ * ctgcn_sim_coo: every non-zero of the finished S in row-major order: row i's at [row_off[i], row_off[i] + row_nnz[i]) of the
+ *   outputs (row_off: device int64[m], the exclusive scan of row_nnz), as (ids[i], ids[j], S[i, j]), ids: device int64[m].
+ * ctgcn_sim_gram_{f32,f64}: out (double[m, m]) = E_r E_rᵀ, E_r row a = E + rows[a]*lde (rows: device int64[m]), fp64 sums over
+ *   k in order; each unordered pair is computed once and mirrored, so out is exactly symmetric.
+ * ctgcn_sim_normalize: x (double[N]) <- (x - min)/(max - min), then x <- x / sum(x): the reference's two normalisations, with
+ *   the sum formed in numpy's order (pairwise within chunks of 8192, chunks in order), so it is numpy's to the bit.
+ *   stats_out (device double[3]) = min, max and the sum after the first step.  workspace: ctgcn_sim_normalize_workspace_bytes.
+ * ctgcn_sim_spearman: xs / ys (double[N]) ascending with no NaN, xi / yi (int64[N]) their source positions (a torch.sort); every
+ *   tie run gets its average rank, scattered back to the source positions, and sums_out (device double[3]) = Σ(rx-μ)(ry-μ),
+ *   Σ(rx-μ)², Σ(ry-μ)² with μ = (N+1)/2.  workspace: ctgcn_sim_spearman_workspace_bytes.
+ * All reductions are per-block partials summed in a fixed order with block counts set by the sizes: repeated calls are bit-identical.
+ */
+int64_t ctgcn_sim_panel_cols(int64_t m, int64_t nnz);
+size_t ctgcn_sim_series_workspace_bytes(int64_t m, int64_t panel);
+int ctgcn_sim_series(int64_t m, const int32_t *row_ptr, const int32_t *col, const double *val, double c, int32_t iter_num, int64_t panel,
+                     int64_t col0, int64_t col1, double *S, void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_sim_finish_workspace_bytes(int64_t m);
+int ctgcn_sim_finish(int64_t m, int32_t pad_zero, double eps, double *S, double *stats_out, int64_t *row_nnz, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int ctgcn_sim_coo(int64_t m, const double *S, const int64_t *row_off, const int64_t *ids, int32_t *row_out, int32_t *col_out,
+                  double *data_out, void *stream);
+int ctgcn_sim_gram_f32(int64_t m, int32_t d, const float *E, int64_t lde, const int64_t *rows, double *out, void *stream);
+int ctgcn_sim_gram_f64(int64_t m, int32_t d, const double *E, int64_t lde, const int64_t *rows, double *out, void *stream);
+size_t ctgcn_sim_normalize_workspace_bytes(int64_t N);
+int ctgcn_sim_normalize(int64_t N, double *x, double *stats_out, void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_sim_spearman_workspace_bytes(int64_t N);
+int ctgcn_sim_spearman(int64_t N, const double *xs, const int64_t *xi, const double *ys, const int64_t *yi, double *sums_out,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
