@@ -17,9 +17,8 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "../../include/ctgcn_hip.h"
-
-extern "C" int ctgcn_set_error_(int code, const char *msg);
+#include "ctgcn_reduce.h"
+#include "ctgcn_try.h"
 
 namespace {
 
@@ -180,20 +179,6 @@ __global__ __launch_bounds__(RT) void slab_reduce_kernel(int64_t n, int blocks, 
     out[v] = s;
 }
 
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int m = RT / 2; m > 0; m >>= 1) {
-        if (t < m) sh[t] += sh[t + m];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 struct EigCtrl {
     int done;
     int stop_step;
@@ -225,7 +210,7 @@ __global__ __launch_bounds__(RT) void eig_spmv_kernel(int64_t n, const int *__re
         y[v] = acc;
         sq += acc * acc;
     }
-    sq = block_sum(sq, sh);
+    sq = block_sum<RT>(sq, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = sq;
 }
 
@@ -235,7 +220,7 @@ __global__ __launch_bounds__(RT) void eig_norm_kernel(int blocks, const double *
     if (ctrl->done) return;
     double s = 0.0;
     for (int b = threadIdx.x; b < blocks; b += RT) s += part[b];
-    s = block_sum(s, sh);
+    s = block_sum<RT>(s, sh);
     if (threadIdx.x == 0) {
         const double nrm = sqrt(s);
         ctrl->norm = nrm == 0.0 ? 1.0 : nrm;
@@ -255,7 +240,7 @@ __global__ __launch_bounds__(RT) void eig_scale_kernel(int64_t n, const double *
         ch += fabs(xn - x[v]);
         x[v] = xn;
     }
-    ch = block_sum(ch, sh);
+    ch = block_sum<RT>(ch, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = ch;
 }
 
@@ -265,7 +250,7 @@ __global__ __launch_bounds__(RT) void eig_test_kernel(int blocks, const double *
     if (ctrl->done) return;
     double s = 0.0;
     for (int b = threadIdx.x; b < blocks; b += RT) s += part[b];
-    s = block_sum(s, sh);
+    s = block_sum<RT>(s, sh);
     if (threadIdx.x == 0 && s < bound) {
         ctrl->done = 1;
         ctrl->stop_step = step;
@@ -414,16 +399,6 @@ __global__ __launch_bounds__(RT) void ridge_sse_kernel(int64_t n, int d, int T, 
 
 }  // namespace
 
-#define CENT_TRY(expr)                                                               \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf[384];                                                           \
-            snprintf(buf, sizeof(buf), "%s -> %s", #expr, hipGetErrorString(e_));   \
-            return ctgcn_set_error_(CTGCN_E_HIP, buf);                               \
-        }                                                                            \
-    } while (0)
-
 extern "C" size_t ctgcn_cent_brandes_workspace_bytes(int64_t n, int64_t s0, int64_t s1)
 {
     if (n < 1 || s0 < 0 || s1 <= s0 || s1 > n) return 0;
@@ -438,7 +413,7 @@ extern "C" int ctgcn_cent_brandes(int64_t n, const int32_t *row_ptr, const int32
     if (!row_ptr || !col || !bc_out || !r_out || !D_out) return ctgcn_set_error_(CTGCN_E_INVALID, "cent_brandes: null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (s1 == s0) {
-        CENT_TRY(hipMemsetAsync(bc_out, 0, sizeof(double) * n, st));
+        CTGCN_TRY(hipMemsetAsync(bc_out, 0, sizeof(double) * n, st));
         return CTGCN_OK;
     }
     if (!workspace || workspace_bytes < ctgcn_cent_brandes_workspace_bytes(n, s0, s1))
@@ -448,7 +423,7 @@ extern "C" int ctgcn_cent_brandes(int64_t n, const int32_t *row_ptr, const int32
     hipLaunchKernelGGL(brandes_kernel, dim3(G), dim3(BT), 0, st, (int)n, row_ptr, col, (int)s0, (int)s1, (char *)workspace, slab, r_out, D_out);
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((n + RT - 1) / RT)), dim3(RT), 0, st, n, G, (int64_t)(slab / sizeof(double)),
                        (const double *)((char *)workspace + sizeof(double) * 2 * n), bc_out);
-    CENT_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -478,10 +453,10 @@ extern "C" int ctgcn_cent_eigenvector(int64_t n, const int32_t *row_ptr, const i
         hipLaunchKernelGGL(eig_scale_kernel, dim3(NB), dim3(RT), 0, st, n, (const double *)y, x_out, part, (const EigCtrl *)ctrl);
         hipLaunchKernelGGL(eig_test_kernel, dim3(1), dim3(RT), 0, st, NB, (const double *)part, bound, it + 1, ctrl);
     }
-    CENT_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     EigCtrl h{};
-    CENT_TRY(hipMemcpyAsync(&h, ctrl, sizeof(EigCtrl), hipMemcpyDeviceToHost, st));
-    CENT_TRY(hipStreamSynchronize(st));
+    CTGCN_TRY(hipMemcpyAsync(&h, ctrl, sizeof(EigCtrl), hipMemcpyDeviceToHost, st));
+    CTGCN_TRY(hipStreamSynchronize(st));
     *stop_step = h.done ? h.stop_step : 0;
     return CTGCN_OK;
 }
@@ -528,7 +503,7 @@ static int ridge_gram(int64_t n, int32_t d, int32_t targets, int32_t folds, cons
     const int64_t per = (int64_t)NR * NC;
     hipLaunchKernelGGL(chunk_reduce_kernel, dim3((unsigned)((per + RT - 1) / RT), folds), dim3(RT), 0, st, per, RIDGE_CHUNKS,
                        (const double *)part, gram_out);
-    CENT_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -567,7 +542,7 @@ static int ridge_sse(int64_t n, int32_t d, int32_t targets, int32_t folds, int32
                        X, ldx, Y, W, (const int *)target_of, part);
     hipLaunchKernelGGL(chunk_reduce_kernel, dim3(1, folds), dim3(RT), 0, st, (int64_t)models, RIDGE_CHUNKS * SSE_SPLIT, (const double *)part,
                        sse_out);
-    CENT_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 

@@ -12,10 +12,9 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "../../include/ctgcn_hip.h"
+#include "ctgcn_logreg.h"
 #include "ctgcn_rng.h"
-
-extern "C" int ctgcn_set_error_(int code, const char *msg);
+#include "ctgcn_try.h"
 
 namespace {
 
@@ -34,13 +33,6 @@ __device__ __forceinline__ double wave_sum(double v)
 #pragma unroll
     for (int m = WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, WAVE);
     return v;
-}
-__device__ __forceinline__ double softplus(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
-__device__ __forceinline__ double sigmoid(double x)
-{
-    if (x >= 0.0) return 1.0 / (1.0 + exp(-x));
-    const double e = exp(x);
-    return e / (1.0 + e);
 }
 
 // exclusive scan of 256 values held one per thread (Hillis-Steele in LDS); returns the thread's exclusive prefix, *total the sum
@@ -342,16 +334,6 @@ size_t negloss_ws(int64_t P, int64_t samples, int64_t nb, int32_t d, char *base,
 
 }  // namespace
 
-#define EP_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf[384];                                                           \
-            snprintf(buf, sizeof(buf), "%s -> %s", #expr, hipGetErrorString(e_));   \
-            return ctgcn_set_error_(CTGCN_E_HIP, buf);                               \
-        }                                                                            \
-    } while (0)
-
 extern "C" size_t ctgcn_epoch_scan_workspace_bytes(int64_t positions)
 {
     return positions < 0 ? 0 : (size_t)(ceil_div(positions, SCAN_TILE) + 1) * sizeof(int64_t);
@@ -369,8 +351,8 @@ extern "C" int ctgcn_neg_sampling_offsets_batched(int64_t positions, const int64
     hipStream_t st = (hipStream_t)stream;
     const int64_t nb = ceil_div(positions, batch_size);
     if (positions == 0) {
-        EP_TRY(hipMemsetAsync(offsets, 0, sizeof(int64_t), st));
-        EP_TRY(hipMemsetAsync(batch_offsets, 0, sizeof(int64_t), st));
+        CTGCN_TRY(hipMemsetAsync(offsets, 0, sizeof(int64_t), st));
+        CTGCN_TRY(hipMemsetAsync(batch_offsets, 0, sizeof(int64_t), st));
         return CTGCN_OK;
     }
     const int64_t ntiles = ceil_div(positions, SCAN_TILE);
@@ -380,7 +362,7 @@ extern "C" int ctgcn_neg_sampling_offsets_batched(int64_t positions, const int64
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(SCAN_T), 0, st, ntiles, tiles, offsets + positions);
     hipLaunchKernelGGL(take_offsets_kernel, dim3((unsigned)ntiles), dim3(SCAN_T), 0, st, positions, perm, pair_row_ptr, (int)num, tiles, offsets);
     hipLaunchKernelGGL(batch_offsets_kernel, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0, st, positions, batch_size, nb, offsets, batch_offsets);
-    EP_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -401,7 +383,7 @@ extern "C" int ctgcn_neg_sampling_indices_batched(int64_t positions, const int64
                            seeds, pair_row_ptr, pair_col, (int)num, offsets, node_out, pos_out);
     hipLaunchKernelGGL(neg_sample_batched_kernel, dim3((unsigned)ceil_div(nb, 64)), dim3(64), 0, st, nb, table_len, neg_table, (int)num, seeds,
                        neg_out, scratch);
-    EP_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -444,7 +426,7 @@ extern "C" int ctgcn_negsampling_loss_fwd_bwd_f32(int64_t positions, int64_t bat
     // dE[neg_{b,j}] += dS_b over every (b, j) (collisions across batches and within one: one run per node)
     hipLaunchKernelGGL(segment_rows_kernel, dim3((unsigned)ceil_div(nb * num, 4)), dim3(256), 0, st, nb * num, (int)d, neg_sorted, neg_order,
                        (const float *)nullptr, (const int64_t *)nullptr, (int64_t)num, (const float *)w.dS, (int64_t)d, dE, ldg);
-    EP_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -472,6 +454,6 @@ extern "C" int ctgcn_reconstruction_loss_fwd_bwd_f32(int64_t positions, int64_t 
     hipLaunchKernelGGL(batch_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, st, positions, batch_size, (int)d, (const double *)lossp, loss_out,
                        (const float *)nullptr, (const int64_t *)nullptr, (const int64_t *)nullptr, (const float *)nullptr, (int64_t)0,
                        (float *)nullptr);
-    EP_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }

@@ -15,10 +15,9 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "../../include/ctgcn_hip.h"
+#include "ctgcn_logreg.h"
 #include "ctgcn_rng.h"
-
-extern "C" int ctgcn_set_error_(int code, const char *msg);
+#include "ctgcn_try.h"
 
 namespace {
 
@@ -30,14 +29,6 @@ constexpr int MAX_GRID = 1024;       // pass blocks (grid-stride over tiles); de
 constexpr int HESS_PARTS = 64;
 
 __device__ __forceinline__ int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-__device__ __forceinline__ double sigmoid(double x)
-{
-    if (x >= 0.0) return 1.0 / (1.0 + exp(-x));
-    const double e = exp(x);
-    return e / (1.0 + e);
-}
-__device__ __forceinline__ double softplus(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
 
 // measure ids: 0 Avg (a+b)/2, 1 Had a*b, 2 L1 |a-b|, 3 L2 (a-b)^2
 __device__ __forceinline__ float feature(int meas, float a, float b)
@@ -231,19 +222,8 @@ __global__ __launch_bounds__(THREADS) void lp_hess_kernel(int64_t n, int64_t chu
     const int meas = (int)((measures >> (2 * m)) & 3u);
     const float *w = W + (int64_t)m * D1;
     int bj[MAXB], bk[MAXB];
-#pragma unroll
-    for (int b = 0; b < MAXB; ++b) {
-        int L = t + b * THREADS, r = 0;
-        if (L >= ntri) { bj[b] = bk[b] = -1; continue; }
-        while (L >= nb - r) { L -= nb - r; ++r; }
-        bj[b] = r;
-        bk[b] = r + L;
-    }
     float acc[MAXB][16];
-#pragma unroll
-    for (int b = 0; b < MAXB; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
+    hess_blocks<MAXB, THREADS>(nb, ntri, bj, bk, acc);
 
     const int64_t lo = (int64_t)p * chunk, hi = min(n, lo + chunk);
     const int wave = t >> 6, lane = t & 63;
@@ -261,52 +241,15 @@ __global__ __launch_bounds__(THREADS) void lp_hess_kernel(int64_t n, int64_t chu
             }
         }
         __syncthreads();
-        {   // z of edge t/8: 8 lanes per edge, fixed-order butterfly
-            const int ee = t >> 3, sub = t & 7;
-            float zp = 0.f;
-            for (int c = sub; c < D1; c += 8) zp += F[ee * D4 + c] * w[c];
-            zp += __shfl_xor(zp, 1, 64);
-            zp += __shfl_xor(zp, 2, 64);
-            zp += __shfl_xor(zp, 4, 64);
-            if (sub == 0) {
-                const int64_t e = e0 + ee;
-                float a = 0.f;
-                if (e < hi) {
-                    const double s = label[e] ? w_pos : w_neg, sg = sigmoid((double)zp);
-                    a = (float)(s * sg * (1.0 - sg));
-                }
-                Aw[ee] = a;
-            }
+        const float zp = hess_row_z(F, D4, D1, w);
+        if ((t & 7) == 0) {
+            const int64_t e = e0 + (t >> 3);
+            Aw[t >> 3] = e < hi ? hess_curvature(label[e] ? w_pos : w_neg, zp) : 0.f;
         }
         __syncthreads();
-        for (int ee = 0; ee < TE; ++ee) {
-            const float a = Aw[ee];
-            const float *fr = F + ee * D4;
-#pragma unroll
-            for (int b = 0; b < MAXB; ++b) {
-                if (bj[b] < 0) continue;
-                const float4 fj = *reinterpret_cast<const float4 *>(fr + 4 * bj[b]);
-                const float4 fk = *reinterpret_cast<const float4 *>(fr + 4 * bk[b]);
-                const float tj[4] = {a * fj.x, a * fj.y, a * fj.z, a * fj.w}, tk[4] = {fk.x, fk.y, fk.z, fk.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) acc[b][r * 4 + c] += tj[r] * tk[c];
-            }
-        }
+        hess_accumulate<MAXB, TE>(F, D4, Aw, bj, bk, acc);
     }
-    float *out = part + ((int64_t)p * M + m) * D1 * D1;
-#pragma unroll
-    for (int b = 0; b < MAXB; ++b) {
-        if (bj[b] < 0) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int jj = 4 * bj[b] + r, kk = 4 * bk[b] + c;
-                if (jj < D1 && kk < D1) out[jj * D1 + kk] = acc[b][r * 4 + c];
-            }
-    }
+    hess_store_upper<MAXB>(part + ((int64_t)p * M + m) * D1 * D1, D1, bj, bk, acc);
 }
 
 // out[v] = Σ_b part[b·stride + v] in block order (fp64)
@@ -339,16 +282,6 @@ int hess_parts(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(H
 
 }  // namespace
 
-#define LP_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf[384];                                                           \
-            snprintf(buf, sizeof(buf), "%s -> %s", #expr, hipGetErrorString(e_));   \
-            return ctgcn_set_error_(CTGCN_E_HIP, buf);                               \
-        }                                                                            \
-    } while (0)
-
 static int check_pass_args(const char *what, int64_t n, int32_t d, int32_t models, int64_t n_nodes, const float *E, int64_t lde,
                            const int64_t *src, const int64_t *dst, const float *W)
 {
@@ -373,13 +306,13 @@ extern "C" int ctgcn_lp_neg_sample(int64_t count, int64_t n_nodes, const int64_t
     if (!from_out || !to_out || !flag || (n_keys > 0 && !keys)) return ctgcn_set_error_(CTGCN_E_INVALID, "lp_neg_sample: null pointer");
     if ((count + THREADS - 1) / THREADS > 0x7fffffffLL) return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, "lp_neg_sample: count too large");
     hipStream_t st = (hipStream_t)stream;
-    LP_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
+    CTGCN_TRY(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(lp_neg_sample_kernel, dim3((unsigned)((count + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, count, n_nodes, keys,
                        n_keys, seed, max_attempts, from_out, to_out, flag);
-    LP_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     int32_t hit = 0;
-    LP_TRY(hipMemcpyAsync(&hit, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    LP_TRY(hipStreamSynchronize(st));
+    CTGCN_TRY(hipMemcpyAsync(&hit, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    CTGCN_TRY(hipStreamSynchronize(st));
     if (hit) return ctgcn_set_error_(CTGCN_E_LIMIT, "lp_neg_sample: a slot reached max_attempts without a valid negative pair");
     return CTGCN_OK;
 }
@@ -400,23 +333,22 @@ extern "C" int ctgcn_lp_grad_f32(int64_t n, int32_t d, int32_t models, uint32_t 
     hipStream_t st = (hipStream_t)stream;
     const int64_t D1 = d + 1, stride = (int64_t)models * D1 + models;
     if (n == 0) {
-        LP_TRY(hipMemsetAsync(grad_out, 0, sizeof(double) * models * D1, st));
-        LP_TRY(hipMemsetAsync(loss_out, 0, sizeof(double) * models, st));
+        CTGCN_TRY(hipMemsetAsync(grad_out, 0, sizeof(double) * models * D1, st));
+        CTGCN_TRY(hipMemsetAsync(loss_out, 0, sizeof(double) * models, st));
         return CTGCN_OK;
     }
     if (workspace_bytes < ctgcn_lp_grad_workspace_bytes(n, d, models)) return ctgcn_set_error_(CTGCN_E_WORKSPACE, "lp_grad: workspace too small");
     const int64_t blocks = pass_blocks(n);
     double *part = (double *)workspace;
-    if (pass_lds(d, models) > 64 * 1024)
-        LP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(lp_pass_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)pass_lds(d, models)));
+    rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(lp_pass_kernel<true>), pass_lds(d, models), "lp_grad");
+    if (rc) return rc;
     hipLaunchKernelGGL(lp_pass_kernel<true>, dim3((unsigned)blocks), dim3(THREADS), pass_lds(d, models), st, n, (int)d, (int)models, measures,
                        n_nodes, E, lde, src, dst, label, w_neg, w_pos, W, part, (float *)nullptr);
     const int64_t ng = (int64_t)models * D1;
     hipLaunchKernelGGL(lp_reduce_kernel, dim3((unsigned)((ng + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, ng, blocks, stride,
                        (const double *)part, grad_out);
     hipLaunchKernelGGL(lp_reduce_kernel, dim3(1), dim3(THREADS), 0, st, (int64_t)models, blocks, stride, (const double *)(part + ng), loss_out);
-    LP_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -428,12 +360,11 @@ extern "C" int ctgcn_lp_scores_f32(int64_t n, int32_t d, int32_t models, uint32_
     if (n == 0) return CTGCN_OK;
     if (!score_out) return ctgcn_set_error_(CTGCN_E_INVALID, "lp_scores: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (pass_lds(d, models) > 64 * 1024)
-        LP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(lp_pass_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)pass_lds(d, models)));
+    rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(lp_pass_kernel<false>), pass_lds(d, models), "lp_scores");
+    if (rc) return rc;
     hipLaunchKernelGGL(lp_pass_kernel<false>, dim3((unsigned)pass_blocks(n)), dim3(THREADS), pass_lds(d, models), st, n, (int)d, (int)models,
                        measures, n_nodes, E, lde, src, dst, (const uint8_t *)nullptr, 0.0, 0.0, W, (double *)nullptr, score_out);
-    LP_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -454,7 +385,7 @@ extern "C" int ctgcn_lp_hess_f32(int64_t n, int32_t d, int32_t models, uint32_t 
     const int D1 = d + 1;
     const int64_t total = (int64_t)models * D1 * D1;
     if (n == 0) {
-        LP_TRY(hipMemsetAsync(hess_out, 0, sizeof(double) * total, st));
+        CTGCN_TRY(hipMemsetAsync(hess_out, 0, sizeof(double) * total, st));
         return CTGCN_OK;
     }
     if (workspace_bytes < ctgcn_lp_hess_workspace_bytes(n, d, models)) return ctgcn_set_error_(CTGCN_E_WORKSPACE, "lp_hess: workspace too small");
@@ -471,6 +402,6 @@ extern "C" int ctgcn_lp_hess_f32(int64_t n, int32_t d, int32_t models, uint32_t 
                            lde, src, dst, label, w_neg, w_pos, W, part);
     hipLaunchKernelGGL(lp_hess_reduce_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (int)models, D1, parts,
                        (const float *)part, hess_out);
-    LP_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }

@@ -23,23 +23,11 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/ctgcn_hip.h"
+#include "ctgcn_try.h"
 #include "ctgcn_jitter.h"
 #include "ctgcn_table.h"           // descriptor tables of the grouped launches: kernel-argument upload + host shadow          // diagnostic builds (-DCTGCN_JITTER): delays around every barrier; nothing in the product
 
-extern "C" int ctgcn_set_error_(int code, const char *msg);   // defined in ctgcn_hip.hip
-
 namespace {
-
-#define GEMM_TRY(expr)                                                               \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf[384];                                                           \
-            snprintf(buf, sizeof(buf), "%s -> %s", #expr, hipGetErrorString(e_));   \
-            return ctgcn_set_error_(CTGCN_E_HIP, buf);                               \
-        }                                                                            \
-    } while (0)
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef f4v f4u __attribute__((aligned(4)));            // a float4 at a 4-byte aligned address
@@ -655,7 +643,7 @@ int ctgcn_split_rows_mapped_(int64_t rows, int32_t k, int32_t kp, const float *x
 {
     if (rows <= 0) return CTGCN_OK;
     launch_split(rows, k, kp, x, ldx, (_Float16 *)p1, (_Float16 *)p2, scale, group_map, group, residual_scale, (hipStream_t)stream);
-    GEMM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -670,7 +658,7 @@ int ctgcn_split_rows_f32(int64_t rows, int32_t k, const float *x, int64_t ldx, v
     _Float16 *p1 = (_Float16 *)planes, *p2 = p1 + (size_t)rows * kp;
     float *sc = (float *)(p2 + (size_t)rows * kp);
     launch_split(rows, k, kp, x, ldx, p1, p2, sc, nullptr, 1, 1.f, (hipStream_t)stream);
-    GEMM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -684,7 +672,7 @@ int ctgcn_pack_weight_f32(int32_t n_out, int32_t k, const float *w, int64_t ldw,
     _Float16 *frags = (_Float16 *)packed;
     float *sb = (float *)(frags + g.frag_halfs);
     hipLaunchKernelGGL(pack_weight_h2_kernel, dim3((unsigned)((g.npad + 3) / 4)), dim3(256), 0, (hipStream_t)stream, n_out, g.npad, k, g.kp, w, ldw, frags, sb);
-    GEMM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -745,7 +733,7 @@ int ctgcn_linear_packed_f32(int64_t rows, int32_t n_out, int32_t k, const void *
         (void)hipFree(a.timeline);
     }
 #endif
-    GEMM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -777,7 +765,7 @@ int ctgcn_linear_packed_chain_f32(int64_t rows, int32_t n_out, int32_t k, const 
     case 3: hipLaunchKernelGGL((gemm_h2_panel_kernel<3, false, true>), grid, blk, 0, (hipStream_t)stream, a); break;
     default: hipLaunchKernelGGL((gemm_h2_panel_kernel<4, false, true>), grid, blk, 0, (hipStream_t)stream, a); break;
     }
-    GEMM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -802,7 +790,7 @@ int ctgcn_linear_packed_group_f32(int32_t groups, int64_t total_rows, int32_t n_
         const _Float16 *frags = (const _Float16 *)w_packed[i];
         host[i] = PanelGroup{frags, (const float *)(frags + g.frag_halfs), bias ? bias[i] : nullptr};
     }
-    GEMM_TRY(ctgcn_table::upload(table, host.data(), host.size() * sizeof(PanelGroup), shadow, (hipStream_t)stream));
+    CTGCN_TRY(ctgcn_table::upload(table, host.data(), host.size() * sizeof(PanelGroup), shadow, (hipStream_t)stream));
     PanelArgs a{};
     a.M = total_rows; a.N = n_out; a.Kp = g.kp;
     a.a1 = (const _Float16 *)planes1; a.a2 = (const _Float16 *)planes2; a.sa = scales;
@@ -819,7 +807,7 @@ int ctgcn_linear_packed_group_f32(int32_t groups, int64_t total_rows, int32_t n_
     case 3: hipLaunchKernelGGL((gemm_h2_panel_kernel<3, true>), grid, blk, 0, (hipStream_t)stream, a); break;
     default: hipLaunchKernelGGL((gemm_h2_panel_kernel<4, true>), grid, blk, 0, (hipStream_t)stream, a); break;
     }
-    GEMM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 

@@ -24,23 +24,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/ctgcn_hip.h"
+#include "ctgcn_try.h"
 #include "ctgcn_jitter.h"          // diagnostic builds (-DCTGCN_JITTER): delays around every barrier; nothing in the product
 
-extern "C" int ctgcn_set_error_(int code, const char *msg);   // defined in ctgcn_hip.hip
 extern "C" int ctgcn_persistent_cus_(int device_cus);         // "
 
 namespace {
-
-#define BWD_TRY(expr)                                                                \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf[384];                                                           \
-            snprintf(buf, sizeof(buf), "%s -> %s", #expr, hipGetErrorString(e_));   \
-            return ctgcn_set_error_(CTGCN_E_HIP, buf);                               \
-        }                                                                            \
-    } while (0)
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
@@ -507,8 +496,8 @@ int device_cus(int *cus)
 {
     int dev = 0;
     *cus = 256;
-    BWD_TRY(hipGetDevice(&dev));
-    BWD_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
+    CTGCN_TRY(hipGetDevice(&dev));
+    CTGCN_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
     *cus = ctgcn_persistent_cus_(*cus);
     return CTGCN_OK;
 }
@@ -548,7 +537,7 @@ int ctgcn_gru_bwd_rec_f32(int64_t rows, int32_t steps, int32_t hidden, const flo
         else hipLaunchKernelGGL((gru_bwd_rec_kernel<false, true>), dim3((unsigned)blocks), dim3(512), 0, (hipStream_t)stream, a);
     } else if (dh_sum) hipLaunchKernelGGL(gru_bwd_rec_kernel<true>, dim3((unsigned)blocks), dim3(512), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(gru_bwd_rec_kernel<false>, dim3((unsigned)blocks), dim3(512), 0, (hipStream_t)stream, a);
-    BWD_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -584,7 +573,7 @@ int ctgcn_gru_bwd_in_f32(int64_t rows, int32_t steps, int32_t hidden, const floa
     else if (x_planes) hipLaunchKernelGGL((gru_bwd_in_kernel<true, false>), dim3((unsigned)blocks), dim3(512), 0, st, a);
     else if (Z) hipLaunchKernelGGL((gru_bwd_in_kernel<false, true>), dim3((unsigned)blocks), dim3(512), 0, st, a);
     else hipLaunchKernelGGL((gru_bwd_in_kernel<false, false>), dim3((unsigned)blocks), dim3(512), 0, st, a);
-    BWD_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 

@@ -32,6 +32,7 @@
 #include "../../include/ctgcn_hip.h"
 #include "ctgcn_jitter.h"
 #include "ctgcn_table.h"          // diagnostic builds (-DCTGCN_JITTER): delays around every barrier; nothing in the product
+#include "ctgcn_try.h"
 
 namespace {
 
@@ -46,11 +47,7 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess) return fail(CTGCN_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+#define HIP_TRY(expr) CTGCN_TRY(expr)
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 

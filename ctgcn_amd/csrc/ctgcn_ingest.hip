@@ -10,21 +10,9 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "../../include/ctgcn_hip.h"
-
-extern "C" int ctgcn_set_error_(int code, const char *msg);   // defined in ctgcn_hip.hip
+#include "ctgcn_try.h"
 
 namespace {
-
-#define ING_TRY(expr)                                                                \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf[384];                                                           \
-            snprintf(buf, sizeof(buf), "%s -> %s", #expr, hipGetErrorString(e_));   \
-            return ctgcn_set_error_(CTGCN_E_HIP, buf);                               \
-        }                                                                            \
-    } while (0)
 
 constexpr uint64_t DROPPED = ~0ull;
 
@@ -133,7 +121,7 @@ extern "C" int ctgcn_edges_to_csr(int64_t n, int64_t m, const int32_t *src, cons
     hipStream_t st = (hipStream_t)stream;
     *nnz_host = 0;
     if (m == 0) {
-        ING_TRY(hipMemsetAsync(row_ptr, 0, (size_t)(n + 1) * 4, st));
+        CTGCN_TRY(hipMemsetAsync(row_ptr, 0, (size_t)(n + 1) * 4, st));
         return CTGCN_OK;
     }
     Layout L{};
@@ -151,23 +139,23 @@ extern "C" int ctgcn_edges_to_csr(int64_t n, int64_t m, const int32_t *src, cons
 
     hipLaunchKernelGGL(pair_keys_kernel, dim3(blocks_m), dim3(256), 0, st, m, (uint64_t)n, src, dst, key_a, idx_a);
     // stable: equal keys keep file order, so the last of a run is the last row of the file
-    ING_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, key_a, key_b, idx_a, idx_b, (size_t)m, 0, 64, st));
+    CTGCN_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, key_a, key_b, idx_a, idx_b, (size_t)m, 0, 64, st));
     hipLaunchKernelGGL(mark_winners_kernel, dim3(blocks_m), dim3(256), 0, st, m, key_b, flag);
     tmp_bytes = L.tmp_bytes;
-    ING_TRY(rocprim::exclusive_scan(tmp, tmp_bytes, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
+    CTGCN_TRY(rocprim::exclusive_scan(tmp, tmp_bytes, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
     uint32_t last_pos = 0, last_flag = 0;
-    ING_TRY(hipMemcpyAsync(&last_pos, pos + (m - 1), 4, hipMemcpyDeviceToHost, st));
-    ING_TRY(hipMemcpyAsync(&last_flag, flag + (m - 1), 4, hipMemcpyDeviceToHost, st));
+    CTGCN_TRY(hipMemcpyAsync(&last_pos, pos + (m - 1), 4, hipMemcpyDeviceToHost, st));
+    CTGCN_TRY(hipMemcpyAsync(&last_flag, flag + (m - 1), 4, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(emit_entries_kernel, dim3(blocks_m), dim3(256), 0, st, m, (uint64_t)n, key_b, idx_b, flag, pos, w, ekey_a, eval_a);
-    ING_TRY(hipStreamSynchronize(st));
+    CTGCN_TRY(hipStreamSynchronize(st));
     const int64_t nnz = 2 * (int64_t)(last_pos + last_flag);
     *nnz_host = nnz;
     if (nnz > 0) {
         tmp_bytes = L.tmp_bytes;
-        ING_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, ekey_a, ekey_b, eval_a, val, (size_t)nnz, 0, key_bits((uint64_t)n), st));
+        CTGCN_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, ekey_a, ekey_b, eval_a, val, (size_t)nnz, 0, key_bits((uint64_t)n), st));
     }
     const int64_t work = (nnz > n + 1 ? nnz : n + 1);
     hipLaunchKernelGGL(finish_csr_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, n, nnz, (uint64_t)n, ekey_b, row_ptr, col_idx);
-    ING_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }

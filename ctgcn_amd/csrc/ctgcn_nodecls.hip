@@ -16,9 +16,8 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "../../include/ctgcn_hip.h"
-
-extern "C" int ctgcn_set_error_(int code, const char *msg);
+#include "ctgcn_logreg.h"
+#include "ctgcn_try.h"
 
 namespace {
 
@@ -54,14 +53,6 @@ __host__ __device__ __forceinline__ int64_t hess_parts_of(int64_t n, int64_t hes
     const int64_t c = (hess_rows(n, hess_max) + HESS_ROWS_PER_PART - 1) / HESS_ROWS_PER_PART;
     return c < 1 ? 1 : (c < MAX_HESS_PARTS ? c : MAX_HESS_PARTS);
 }
-
-__device__ __forceinline__ double sigmoid(double x)
-{
-    if (x >= 0.0) return 1.0 / (1.0 + exp(-x));
-    const double e = exp(x);
-    return e / (1.0 + e);
-}
-__device__ __forceinline__ double softplus(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
 
 // largest i in [0, count) with start[i] <= v (start non-decreasing, start[0] <= v)
 template <typename T>
@@ -329,70 +320,22 @@ __global__ __launch_bounds__(THREADS) void nc_hess_kernel(Table tb, int d, int M
     const int64_t chunk = (nsub + parts - 1) / parts, lo = c * chunk, hi = min(nsub, lo + chunk);
 
     int bj[MAXB], bk[MAXB];
-#pragma unroll
-    for (int q = 0; q < MAXB; ++q) {
-        int L = t + q * THREADS, r = 0;
-        if (L >= ntri) { bj[q] = bk[q] = -1; continue; }
-        while (L >= nb - r) { L -= nb - r; ++r; }
-        bj[q] = r;
-        bk[q] = r + L;
-    }
     float acc[MAXB][16];
-#pragma unroll
-    for (int q = 0; q < MAXB; ++q)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[q][i] = 0.f;
+    hess_blocks<MAXB, THREADS>(nb, ntri, bj, bk, acc);
 
     for (int64_t e0 = lo; e0 < hi; e0 += TE) {
         __syncthreads();
         gather_tile(F, D4, d, tb.rows, rs, step, e0, hi, n_emb, E, lde);
         __syncthreads();
-        {   // z of row t/8: 8 lanes per row, fixed-order butterfly
-            const int ee = t >> 3, sub = t & 7;
-            float zp = 0.f;
-            for (int cc = sub; cc < D1; cc += 8) zp += F[ee * D4 + cc] * w[cc];
-            zp += __shfl_xor(zp, 1, 64);
-            zp += __shfl_xor(zp, 2, 64);
-            zp += __shfl_xor(zp, 4, 64);
-            if (sub == 0) {
-                const int64_t i = e0 + ee;
-                float a = 0.f;
-                if (i < hi) {
-                    const double s = tb.y[rs + i * step] == pos ? w_pos : w_neg, sg = sigmoid((double)zp);
-                    a = (float)(s * sg * (1.0 - sg));
-                }
-                Aw[ee] = a;
-            }
+        const float zp = hess_row_z(F, D4, D1, w);
+        if ((t & 7) == 0) {
+            const int64_t i = e0 + (t >> 3);
+            Aw[t >> 3] = i < hi ? hess_curvature(tb.y[rs + i * step] == pos ? w_pos : w_neg, zp) : 0.f;
         }
         __syncthreads();
-        for (int ee = 0; ee < TE; ++ee) {
-            const float a = Aw[ee];
-            const float *fr = F + ee * D4;
-#pragma unroll
-            for (int q = 0; q < MAXB; ++q) {
-                if (bj[q] < 0) continue;
-                const float4 fj = *reinterpret_cast<const float4 *>(fr + 4 * bj[q]);
-                const float4 fk = *reinterpret_cast<const float4 *>(fr + 4 * bk[q]);
-                const float tj[4] = {a * fj.x, a * fj.y, a * fj.z, a * fj.w}, tk[4] = {fk.x, fk.y, fk.z, fk.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int cc = 0; cc < 4; ++cc) acc[q][r * 4 + cc] += tj[r] * tk[cc];
-            }
-        }
+        hess_accumulate<MAXB, TE>(F, D4, Aw, bj, bk, acc);
     }
-    float *out = part + (b * MM + lm) * (int64_t)D1 * D1;
-#pragma unroll
-    for (int q = 0; q < MAXB; ++q) {
-        if (bj[q] < 0) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) {
-                const int jj = 4 * bj[q] + r, kk = 4 * bk[q] + cc;
-                if (jj < D1 && kk < D1) out[jj * D1 + kk] = acc[q][r * 4 + cc];
-            }
-    }
+    hess_store_upper<MAXB>(part + (b * MM + lm) * (int64_t)D1 * D1, D1, bj, bk, acc);
 }
 
 // hess[m][j][k] = Σ over the parts of m's problem of part[.][lm][min(j,k)][max(j,k)] in part order (fp64); zero for flagged models
@@ -419,16 +362,6 @@ size_t pass_lds(int d, int gm) { return sizeof(double) * THREADS + sizeof(float)
 
 }  // namespace
 
-#define NC_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf[384];                                                           \
-            snprintf(buf, sizeof(buf), "%s -> %s", #expr, hipGetErrorString(e_));   \
-            return ctgcn_set_error_(CTGCN_E_HIP, buf);                               \
-        }                                                                            \
-    } while (0)
-
 static int check_table(const char *what, int32_t problems, int32_t d, int64_t blocks, const int64_t *row_start, const int64_t *block_start,
                        const int64_t *rows, const int32_t *y, const int32_t *model_start, const int32_t *model_flag, int64_t n_emb,
                        const float *E, int64_t lde, const float *W, int64_t models)
@@ -446,13 +379,6 @@ static int check_table(const char *what, int32_t problems, int32_t d, int64_t bl
         snprintf(buf, sizeof(buf), "%s: null pointer", what);
         return ctgcn_set_error_(CTGCN_E_INVALID, buf);
     }
-    return CTGCN_OK;
-}
-
-static int set_lds(const void *fn, size_t bytes)
-{
-    if (bytes > 160 * 1024) return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, "nodecls: LDS need above 160 KiB");
-    if (bytes > 64 * 1024) NC_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return CTGCN_OK;
 }
 
@@ -486,14 +412,14 @@ extern "C" int ctgcn_nc_grad_f32(int32_t problems, int32_t d, int32_t max_models
     const int G = (max_models + gm - 1) / gm;
     const Table tb{problems, row_start, chunk_start, rows, y, model_start, model_pos, model_w, model_flag};
     const size_t lds = pass_lds(d, gm);
-    if ((rc = set_lds(reinterpret_cast<const void *>(nc_pass_kernel<false>), lds))) return rc;
+    if ((rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(nc_pass_kernel<false>), lds, "nodecls"))) return rc;
     double *part = (double *)workspace;
     hipLaunchKernelGGL(nc_pass_kernel<false>, dim3((unsigned)total_chunks, (unsigned)G), dim3(THREADS), lds, st, tb, (int)d, gm, 0,
                        (const int32_t *)nullptr, n_emb, E, lde, W, models, part, (int32_t *)nullptr, (unsigned long long *)nullptr);
     const int64_t nout = models * (d + 2);
     hipLaunchKernelGGL(nc_grad_reduce_kernel, dim3((unsigned)((nout + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, tb, (int)d, gm, G,
                        (const double *)part, models, grad_out, loss_out);
-    NC_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -530,7 +456,7 @@ extern "C" int ctgcn_nc_hess_f32(int32_t problems, int32_t d, int32_t max_models
     const int64_t total = models * D1 * D1;
     hipLaunchKernelGGL(nc_hess_reduce_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, tb, (int)d,
                        (int)max_models, (const float *)part, models, hess_out);
-    NC_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -547,7 +473,7 @@ extern "C" int ctgcn_nc_predict_f32(int32_t problems, int32_t d, int32_t max_cla
     if (max_classes > group_max(d)) return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, "nc_predict: more classes than models per block");
     if (!n_classes || !pred_out || !correct_out) return ctgcn_set_error_(CTGCN_E_INVALID, "nc_predict: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    NC_TRY(hipMemsetAsync(correct_out, 0, sizeof(int64_t) * problems * groups, st));
+    CTGCN_TRY(hipMemsetAsync(correct_out, 0, sizeof(int64_t) * problems * groups, st));
     if (models == 0) return CTGCN_OK;
     const int mpg = max_classes == 2 ? 1 : max_classes;
     const int gm = std::min(group_max(d), groups * mpg);
@@ -556,9 +482,9 @@ extern "C" int ctgcn_nc_predict_f32(int32_t problems, int32_t d, int32_t max_cla
     if (G > 0xffff) return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, "nc_predict: too many C groups");
     const Table tb{problems, row_start, chunk_start, rows, y, model_start, nullptr, nullptr, model_flag};
     const size_t lds = pass_lds(d, gm);
-    if ((rc = set_lds(reinterpret_cast<const void *>(nc_pass_kernel<true>), lds))) return rc;
+    if ((rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(nc_pass_kernel<true>), lds, "nodecls"))) return rc;
     hipLaunchKernelGGL(nc_pass_kernel<true>, dim3((unsigned)total_chunks, (unsigned)G), dim3(THREADS), lds, st, tb, (int)d, gm, (int)groups,
                        n_classes, n_emb, E, lde, W, models, (double *)nullptr, pred_out, (unsigned long long *)correct_out);
-    NC_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }

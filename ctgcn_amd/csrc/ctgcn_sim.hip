@@ -18,11 +18,10 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "../../include/ctgcn_hip.h"
+#include "ctgcn_reduce.h"
+#include "ctgcn_try.h"
 
 #pragma clang fp contract(off)
-
-extern "C" int ctgcn_set_error_(int code, const char *msg);
 
 namespace {
 
@@ -245,19 +244,6 @@ __global__ __launch_bounds__(ST) void sim_gram_kernel(int64_t m, int d, const T 
     }
 }
 
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = RB / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // part[b*2 + {0, 1}] = min, max of x over block b's grid-stride share
 __global__ __launch_bounds__(RB) void sim_minmax_kernel(int64_t N, const double *__restrict__ x, double *__restrict__ part)
 {
@@ -376,7 +362,7 @@ __global__ __launch_bounds__(RB) void sim_sum_reduce_kernel(int64_t count, int k
     for (int q = 0; q < k; ++q) {
         double s = 0.0;
         for (int64_t b = threadIdx.x; b < count; b += RB) s = s + part[b * k + q];
-        const double r = block_sum(s, sh);
+        const double r = block_sum<RB>(s, sh);
         if (threadIdx.x == 0) out[q] = r;
     }
 }
@@ -422,9 +408,9 @@ __global__ __launch_bounds__(RB) void sim_corr_kernel(int64_t N, const double *_
         sxx = sxx + dx * dx;
         syy = syy + dy * dy;
     }
-    sxy = block_sum(sxy, sh);
-    sxx = block_sum(sxx, sh);
-    syy = block_sum(syy, sh);
+    sxy = block_sum<RB>(sxy, sh);
+    sxx = block_sum<RB>(sxx, sh);
+    syy = block_sum<RB>(syy, sh);
     if (threadIdx.x == 0) {
         part[3 * blockIdx.x] = sxy;
         part[3 * blockIdx.x + 1] = sxx;
@@ -433,16 +419,6 @@ __global__ __launch_bounds__(RB) void sim_corr_kernel(int64_t N, const double *_
 }
 
 }  // namespace
-
-#define SIM_TRY(expr)                                                                \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf[384];                                                           \
-            snprintf(buf, sizeof(buf), "%s -> %s", #expr, hipGetErrorString(e_));   \
-            return ctgcn_set_error_(CTGCN_E_HIP, buf);                               \
-        }                                                                            \
-    } while (0)
 
 static inline unsigned blocks_of(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
 
@@ -494,7 +470,7 @@ extern "C" int ctgcn_sim_series(int64_t m, const int32_t *row_ptr, const int32_t
             dst = t;
         }
     }
-    SIM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -520,7 +496,7 @@ extern "C" int ctgcn_sim_finish(int64_t m, int32_t pad_zero, double eps, double 
     hipLaunchKernelGGL(sim_sym_kernel, dim3((unsigned)T, (unsigned)T), dim3(ST), 0, st, m, T, S, part);
     hipLaunchKernelGGL(sim_minmax_reduce_kernel, dim3(1), dim3(RB), 0, st, T * T, (const double *)part, (int)(pad_zero != 0), stats_out);
     hipLaunchKernelGGL(sim_norm_kernel, dim3((unsigned)m), dim3(ST), 0, st, m, S, (const double *)stats_out, eps, row_nnz);
-    SIM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -531,7 +507,7 @@ extern "C" int ctgcn_sim_coo(int64_t m, const double *S, const int64_t *row_off,
     if (m > 0x7fffffffLL) return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, "sim_coo: m over 2^31 - 1");
     if (!S || !row_off || !ids || !row_out || !col_out || !data_out) return ctgcn_set_error_(CTGCN_E_INVALID, "sim_coo: null pointer");
     hipLaunchKernelGGL(sim_coo_kernel, dim3((unsigned)m), dim3(ST), 0, (hipStream_t)stream, m, S, row_off, ids, row_out, col_out, data_out);
-    SIM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -553,7 +529,7 @@ static int sim_gram(const char *name, int64_t m, int32_t d, const T *E, int64_t 
         return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, buf);
     }
     hipLaunchKernelGGL(sim_gram_kernel<T>, dim3((unsigned)Tn, (unsigned)Tn), dim3(ST), 0, (hipStream_t)stream, m, (int)d, E, lde, rows, out);
-    SIM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -590,7 +566,7 @@ extern "C" int ctgcn_sim_normalize(int64_t N, double *x, double *stats_out, void
     hipLaunchKernelGGL(sim_np_chunk_kernel, dim3(blocks_of(chunks, RB)), dim3(RB), 0, st, N, (const double *)x, part);
     hipLaunchKernelGGL(sim_np_total_kernel, dim3(1), dim3(64), 0, st, chunks, (const double *)part, stats_out + 2);
     hipLaunchKernelGGL(sim_div_kernel, dim3((unsigned)G), dim3(RB), 0, st, N, x, (const double *)stats_out);
-    SIM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -615,6 +591,6 @@ extern "C" int ctgcn_sim_spearman(int64_t N, const double *xs, const int64_t *xi
     hipLaunchKernelGGL(sim_corr_kernel, dim3((unsigned)G), dim3(RB), 0, st, N, (const double *)rx, (const double *)ry,
                        ((double)N + 1.0) * 0.5, part);
     hipLaunchKernelGGL(sim_sum_reduce_kernel, dim3(1), dim3(RB), 0, st, G, 3, (const double *)part, sums_out);
-    SIM_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }

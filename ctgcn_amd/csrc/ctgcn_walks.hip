@@ -9,10 +9,8 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "../../include/ctgcn_hip.h"
+#include "ctgcn_try.h"
 #include "ctgcn_rng.h"
-
-extern "C" int ctgcn_set_error_(int code, const char *msg);
 
 namespace {
 
@@ -113,23 +111,13 @@ __global__ void neg_sample_kernel(int64_t table_len, const int32_t *__restrict__
 
 }  // namespace
 
-#define WK_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf[384];                                                           \
-            snprintf(buf, sizeof(buf), "%s -> %s", #expr, hipGetErrorString(e_));   \
-            return ctgcn_set_error_(CTGCN_E_HIP, buf);                               \
-        }                                                                            \
-    } while (0)
-
 extern "C" int ctgcn_row_cumsum_f32(int64_t n, const int32_t *row_ptr, const float *val, float *cumw, void *stream)
 {
     if (n < 0) return ctgcn_set_error_(CTGCN_E_INVALID, "row_cumsum: bad size");
     if (n == 0) return CTGCN_OK;
     if (!row_ptr) return ctgcn_set_error_(CTGCN_E_INVALID, "row_cumsum: null pointer");
     hipLaunchKernelGGL(row_cumsum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, row_ptr, val, cumw);
-    WK_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -145,7 +133,7 @@ extern "C" int ctgcn_random_walk_pairs(int64_t n, const int32_t *row_ptr, const 
     if ((threads + 255) / 256 > 0x7fffffffLL) return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, "random_walk_pairs: too many walks per call");
     hipLaunchKernelGGL(walk_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, walk_len, (int)walk_time,
                        (int)first_walk, seed, weighted, row_ptr, col_idx, cumw, pair_src, pair_dst, (unsigned long long *)freq);
-    WK_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
 
@@ -161,6 +149,6 @@ extern "C" int ctgcn_neg_sampling_indices(int64_t batch, const int64_t *batch_no
         hipLaunchKernelGGL(pos_sample_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, batch, batch_nodes,
                            pair_row_ptr, pair_col, (int)num, seed, offsets, node_out, pos_out);
     hipLaunchKernelGGL(neg_sample_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, table_len, neg_table, (int)num, seed ^ 0xabcdefull, neg_out, scratch);
-    WK_TRY(hipGetLastError());
+    CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }

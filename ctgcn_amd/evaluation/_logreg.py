@@ -12,19 +12,20 @@ changes the number of iterations), and one batched fp64 Cholesky solves all Newt
 """
 import warnings
 from dataclasses import dataclass
+from functools import partial
 
 import torch
 
 from .. import _lib
 from .._lib import check, ptr
+from . import _common, _newton
+from ._common import stream as _stream
 
 MEASURES = ("Avg", "Had", "L1", "L2")
 MAX_MODELS = 16          # models per kernel pass (ctgcn_eval.hip); more are fitted in several groups
 
 
-def require_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA (ROCm) tensor: link-prediction evaluation runs on the GPU, no CPU fallback" % what)
+require_cuda = partial(_common.require_cuda, task="link-prediction")
 
 
 def measure_code(measures):
@@ -70,10 +71,6 @@ class EdgeSet:
         sub.n_neg = sub.n - sub.n_pos
         sub.w_pos, sub.w_neg = self.w_pos, self.w_neg
         return sub
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _check_emb(E):
@@ -140,15 +137,6 @@ class FitReport:
     grad_norm: float      # max |∇f| of sklearn's scaled objective at the returned parameters
 
 
-def _objective(E, es, measures, theta, inv_cn):
-    loss, g = loss_grad(E, es, measures, theta)
-    w = theta[:, :-1]
-    f = loss / es.n + 0.5 * inv_cn * (w * w).sum(1)
-    g = g / es.n
-    g[:, :-1] += inv_cn[:, None] * w
-    return f, g
-
-
 def _fit_group(E, es, hs, measures, Cs, tol, max_iter):
     M, D1 = len(measures), E.shape[1] + 1
     dev = E.device
@@ -156,45 +144,25 @@ def _fit_group(E, es, hs, measures, Cs, tol, max_iter):
     reg = torch.zeros(M, D1, D1, dtype=torch.float64, device=dev)
     idx = torch.arange(D1 - 1, device=dev)
     reg[:, idx, idx] = inv_cn[:, None]
-    theta = torch.zeros(M, D1, dtype=torch.float64, device=dev)
-    f, g = _objective(E, es, measures, theta, inv_cn)
-    iters = [0] * M
-    for _ in range(max_iter):
-        gmax = g.abs().amax(1)
-        active = gmax > tol
-        if not bool(active.any()):
-            break
-        for m in torch.nonzero(active).flatten().tolist():
-            iters[m] += 1
-        H = hessian(E, hs, measures, theta.to(torch.float32)) / hs.n + reg
-        L, info = torch.linalg.cholesky_ex(H)
-        if bool((info > 0).any()):            # numerically singular (saturated fits): damp those systems
-            damp = (info > 0).to(torch.float64) * 1e-10 * H.diagonal(dim1=1, dim2=2).abs().amax(1).clamp_min(1e-30)
-            H = H + damp[:, None, None] * torch.eye(D1, dtype=torch.float64, device=dev)
-            L = torch.linalg.cholesky(H)
-        p = -torch.cholesky_solve(g.unsqueeze(2), L).squeeze(2)
-        p[~active] = 0
-        slope = (g * p).sum(1)
-        t = torch.ones(M, dtype=torch.float64, device=dev)
-        done = ~active
-        for _ls in range(40):
-            trial = torch.where(done[:, None], theta, theta + t[:, None] * p)
-            f_new, g_new = _objective(E, es, measures, trial, inv_cn)
-            armijo = f_new <= f + 1e-4 * t * slope
-            # near the optimum the decrease of f sinks below its rounding floor (fp32 z per edge) while ∇f is still accurate to
-            # ~1e-9: there, a step that lowers max|∇f| is progress
-            ok = (armijo | (g_new.abs().amax(1) < gmax)) & ~done
-            theta = torch.where(ok[:, None], trial, theta)
-            f = torch.where(ok, f_new, f)
-            g = torch.where(ok[:, None], g_new, g)
-            done = done | ok
-            if bool(done.all()):
-                break
-            t = torch.where(done, t, 0.5 * t)
-        if not bool(done.all()):
-            break                              # no descent left for some model: stop and report
-    gmax = g.abs().amax(1).tolist()
+
+    def objective(theta, live):                 # every model of a group is evaluated: the pass has no per-model skip
+        loss, g = loss_grad(E, es, measures, theta)
+        w = theta[:, :-1]
+        f = loss / es.n + 0.5 * inv_cn * (w * w).sum(1)
+        g = g / es.n
+        g[:, :-1] += inv_cn[:, None] * w
+        return f, g
+
+    def hessians(theta, active):                # one call on the strided subsample; inactive systems are solved as they are
+        yield 0, M, hessian(E, hs, measures, theta.to(torch.float32)) / hs.n + reg
+
+    theta, iters, gmax = _newton.minimize(torch.zeros(M, D1, dtype=torch.float64, device=dev), objective, hessians, tol, max_iter)
     return theta, [FitReport(measures[m], float(Cs[m]), gmax[m] <= tol, iters[m], gmax[m]) for m in range(M)]
+
+
+def groups(n_models):
+    """The [s, e) ranges of at most MAX_MODELS models that one kernel pass takes."""
+    return [(s, min(s + MAX_MODELS, n_models)) for s in range(0, n_models, MAX_MODELS)]
 
 
 def fit(E, train, measures, Cs, tol=1e-6, max_iter=100, hess_max=1 << 18):
@@ -205,8 +173,8 @@ def fit(E, train, measures, Cs, tol=1e-6, max_iter=100, hess_max=1 << 18):
         raise ValueError("This solver needs samples of at least 2 classes in the data, but the train set has only one class")
     hs = train.subsample(hess_max)
     thetas, reports = [], []
-    for s in range(0, len(measures), MAX_MODELS):
-        th, rep = _fit_group(E, train, hs, list(measures[s:s + MAX_MODELS]), list(Cs[s:s + MAX_MODELS]), tol, max_iter)
+    for s, e in groups(len(measures)):
+        th, rep = _fit_group(E, train, hs, list(measures[s:e]), list(Cs[s:e]), tol, max_iter)
         thetas.append(th)
         reports += rep
     for r in reports:
@@ -214,6 +182,11 @@ def fit(E, train, measures, Cs, tol=1e-6, max_iter=100, hess_max=1 << 18):
             warnings.warn("logistic regression (%s, C=%g) did not converge: max|grad| %.3g > tol %.3g after %d Newton iterations"
                           % (r.measure, r.C, r.grad_norm, tol, r.iterations), RuntimeWarning)
     return torch.cat(thetas), reports
+
+
+def scores_all(E, es, measures, W):
+    """scores() of any number of models, MAX_MODELS per pass."""
+    return torch.cat([scores(E, es, measures[s:e], W[s:e]) for s, e in groups(len(measures))])
 
 
 def roc_auc(labels, score):

@@ -8,25 +8,26 @@ rows is sklearn's _ConstantPredictor (probability 0 or 1) and is not fitted.
 
 fit() runs batched Newton over every model of every problem: per iteration one gradient pass and one Hessian pass over all problems
 (each row tile gathered once for all models of its problem) and one batched fp64 Cholesky, in bounded chunks of models, with a per-model
-active mask and the backtracking rule of _logreg._fit_group.  A model stops when max |∇f| <= tol.
+active mask, by the driver of _newton.py.  A model stops when max |∇f| <= tol.
 """
 import warnings
 from dataclasses import dataclass
+from functools import partial
 
 import numpy as np
 import torch
 
 from .. import _lib
 from .._lib import check, ptr
-from ._logreg import _check_emb, _hi_lo, _stream, balanced_weights
+from . import _common, _newton
+from ._common import stream as _stream
+from ._logreg import _check_emb, _hi_lo, balanced_weights
 
 FLAG_FIT, FLAG_ZERO, FLAG_ONE = 0, 1, 2
 HESS_BYTES = 1 << 28          # bound on one Hessian call's partials and output
 
 
-def require_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA (ROCm) tensor: node-classification evaluation runs on the GPU, no CPU fallback" % what)
+require_cuda = partial(_common.require_cuda, task="node-classification")
 
 
 def models_per_group(K):
@@ -198,11 +199,15 @@ def fit(table, tol=1e-6, max_iter=100):
     inv_cn = torch.tensor([1.0 / (C * max(k, 1)) for C, k in zip(table.m_C, table.m_n)], dtype=torch.float64, device=dev)
     n_sub = torch.tensor([max(int(table.n_sub[p]), 1) for p in table.m_problem], dtype=torch.float64, device=dev)
     fitted = torch.from_numpy(table.flags_h == FLAG_FIT).to(dev)
-    theta = torch.zeros(M, D1, dtype=torch.float64, device=dev)
     eye = torch.eye(D1, dtype=torch.float64, device=dev)
+    idx = torch.arange(D1 - 1, device=dev)
+    chunks = table.hess_chunks()
 
-    def objective(th, flags=None):
-        loss, g = table.loss_grad(th, flags)
+    def flags_for(mask):            # kernels skip every model outside mask
+        return torch.where(mask, table.model_flag, torch.full_like(table.model_flag, FLAG_ZERO)).contiguous()
+
+    def objective(th, live):
+        loss, g = table.loss_grad(th, None if live is None else flags_for(live))
         w = th[:, :-1]
         f = loss / n_m + 0.5 * inv_cn * (w * w).sum(1)
         g = g / n_m[:, None]
@@ -210,56 +215,18 @@ def fit(table, tol=1e-6, max_iter=100):
         g[~fitted] = 0
         return f, g
 
-    def flags_for(mask):            # kernels skip every model outside mask
-        return torch.where(mask, table.model_flag, torch.full_like(table.model_flag, FLAG_ZERO)).contiguous()
-
-    f, g = objective(theta)
-    iters = torch.zeros(M, dtype=torch.int64, device=dev)
-    chunks = table.hess_chunks()
-    for _ in range(max_iter):
-        gmax = g.abs().amax(1)
-        active = (gmax > tol) & fitted
-        if not bool(active.any()):
-            break
-        iters += active.to(torch.int64)
+    def hessians(th, active):       # in chunks of problems within HESS_BYTES; those without an active model are left out
         hflags = flags_for(active)
-        p = torch.zeros(M, D1, dtype=torch.float64, device=dev)
         for p0, p1 in chunks:
             m0, m1 = int(table.model_start_h[p0]), int(table.model_start_h[p1])
             if m1 == m0 or not bool(active[m0:m1].any()):
                 continue
-            H = table.hessian(theta, p0, p1, hflags) / n_sub[m0:m1, None, None]
-            idx = torch.arange(D1 - 1, device=dev)
+            H = table.hessian(th, p0, p1, hflags) / n_sub[m0:m1, None, None]
             H[:, idx, idx] += inv_cn[m0:m1, None]
             H[~active[m0:m1]] = eye                      # inactive systems: identity (their step is discarded)
-            L, info = torch.linalg.cholesky_ex(H)
-            if bool((info > 0).any()):                    # numerically singular (saturated fits): damp those systems
-                damp = (info > 0).to(torch.float64) * 1e-10 * H.diagonal(dim1=1, dim2=2).abs().amax(1).clamp_min(1e-30)
-                H = H + damp[:, None, None] * eye
-                L = torch.linalg.cholesky(H)
-            p[m0:m1] = -torch.cholesky_solve(g[m0:m1].unsqueeze(2), L).squeeze(2)
-        p[~active] = 0
-        slope = (g * p).sum(1)
-        t = torch.ones(M, dtype=torch.float64, device=dev)
-        done = ~active
-        for _ls in range(40):
-            trial = torch.where(done[:, None], theta, theta + t[:, None] * p)
-            f_new, g_new = objective(trial, flags_for(~done))
-            armijo = f_new <= f + 1e-4 * t * slope
-            # near the optimum the decrease of f sinks below its rounding floor while ∇f is still accurate: there, a step that
-            # lowers max|∇f| is progress (as in _logreg._fit_group)
-            ok = (armijo | (g_new.abs().amax(1) < gmax)) & ~done
-            theta = torch.where(ok[:, None], trial, theta)
-            f = torch.where(ok, f_new, f)
-            g = torch.where(ok[:, None], g_new, g)
-            done = done | ok
-            if bool(done.all()):
-                break
-            t = torch.where(done, t, 0.5 * t)
-        if not bool(done.all()):
-            break                                          # no descent left for some model: stop and report
-    gmax = g.abs().amax(1).tolist()
-    it = iters.tolist()
+            yield m0, m1, H
+
+    theta, it, gmax = _newton.minimize(torch.zeros(M, D1, dtype=torch.float64, device=dev), objective, hessians, tol, max_iter, fitted)
     reports = [FitReport(table.m_problem[m], table.m_cls[m], table.m_C[m], table.flags_h[m] != FLAG_FIT or gmax[m] <= tol, it[m],
                          gmax[m], bool(table.flags_h[m] != FLAG_FIT)) for m in range(M)]
     for r in reports:

@@ -14,6 +14,7 @@ the other.  What runs differently:
 import ctypes
 import os
 import time
+from functools import partial
 
 import numpy as np
 import pandas as pd
@@ -21,7 +22,9 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check, ptr
-from ..utils import read_edge_rows, symmetric_csr_from_rows
+from ..utils import symmetric_csr_from_rows
+from . import _common
+from ._common import method_snapshots, read_embedding, read_nodes as _read_nodes, snapshot_rows, stream as _stream
 
 CENTRALITY_LIST = ('closeness', 'betweenness', 'eigenvector', 'kcore')
 ALL_KINDS = ('degree',) + CENTRALITY_LIST
@@ -35,21 +38,8 @@ class PowerIterationFailedConvergence(RuntimeError):
         self.max_iter = max_iter
 
 
-def _device(device=None):
-    if device is not None:
-        return torch.device(device)
-    if not torch.cuda.is_available():
-        raise RuntimeError("centrality-prediction evaluation needs a ROCm GPU: no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _require_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA (ROCm) tensor: centrality-prediction evaluation runs on the GPU, no CPU fallback" % what)
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
+_device = partial(_common.device, task="centrality-prediction")
+_require_cuda = partial(_common.require_cuda, task="centrality-prediction")
 
 
 def _csr(row_ptr, col):
@@ -64,11 +54,7 @@ def graph_csr(file_path, full_node_list, sep='\t'):
     """(row_ptr, col) int32 numpy arrays of the reference's graph of a snapshot file: every pair in the file is an edge whatever its
     weight (zero included), duplicates collapse, self loops are dropped, and every node of full_node_list is a vertex.  A node in the
     file but not in full_node_list raises ValueError."""
-    node2idx = dict(zip([str(v) for v in full_node_list], range(len(full_node_list))))
-    try:
-        src, dst, _ = read_edge_rows(file_path, node2idx, sep)
-    except KeyError as e:
-        raise ValueError("%s names a node that is not in the node file (the reference would add it as a vertex): %s" % (file_path, e))
+    src, dst, _ = snapshot_rows(file_path, full_node_list, sep, " (the reference would add it as a vertex)")
     # weight 1 everywhere: the structure is what counts, and an explicit zero weight must still be an edge
     m = symmetric_csr_from_rows(src, dst, np.ones(len(src)), len(full_node_list))
     return m.indptr.astype(np.int32), m.indices.astype(np.int32)
@@ -254,10 +240,6 @@ def evaluate(embedding, row_ptr, col, alpha_list, split_fold=5, date=None, max_i
     return [date] + min_over_alphas(ridge_cv_errors(embedding, Y, alpha_list, split_fold))
 
 
-def _read_nodes(node_file_path):
-    return pd.read_csv(node_file_path, names=['node'])['node'].tolist()
-
-
 class DataGenerator(object):
     """Reference DataGenerator: writes <date>_centrality.csv (node, closeness, betweenness, eigenvector, kcore; sep = file_sep)."""
 
@@ -336,17 +318,12 @@ class CentralityPredictor(object):
         return [date] + min_over_alphas(errors)
 
     def centrality_prediction_all_time(self, method):
-        f_list = sorted(os.listdir(self.origin_base_path))
         all_mse_list = []
-        for f_name in f_list:
-            date = f_name.split('.')[0]
-            cur_embedding_path = os.path.join(self.embedding_base_path, method, f_name)
-            if not os.path.exists(cur_embedding_path):
-                continue
+        for date, _, cur_embedding_path in method_snapshots(self.origin_base_path, self.embedding_base_path, method):
             df_centrality = pd.read_csv(os.path.join(self.centrality_base_path, date + '_centrality.csv'), sep=self.file_sep)
             centrality_data = df_centrality.iloc[:, 1:].values
-            df_embedding = pd.read_csv(cur_embedding_path, sep=self.file_sep, index_col=0).loc[self.full_node_list]
-            all_mse_list.append(self.get_prediction_error(centrality_data, df_embedding.values.astype(np.float64), date))
+            embedding = read_embedding(cur_embedding_path, self.file_sep, self.full_node_list, np.float64)
+            all_mse_list.append(self.get_prediction_error(centrality_data, embedding, date))
         df_output = pd.DataFrame(all_mse_list, columns=['date'] + list(CENTRALITY_LIST))
         print(df_output)
         df_output.to_csv(os.path.join(self.output_base_path, method + '_mse_record.csv'), sep=',', index=False)

@@ -13,6 +13,7 @@ with splits drawn by the GPU sampler.
 import os
 import time
 import zlib
+from functools import partial
 
 import numpy as np
 import pandas as pd
@@ -20,19 +21,15 @@ import torch
 
 from .. import _lib
 from .._lib import check, ptr
-from . import _logreg
+from . import _common, _logreg
+from ._common import aggregate_stats, method_snapshots, read_embedding, read_nodes, select_C
 from ._logreg import EdgeSet, require_cuda, roc_auc
 
 ALL_MEASURES = ("Avg", "Had", "L1", "L2", "sigmoid")
 MAX_ATTEMPTS = 1 << 20        # draws per negative slot before the sampler gives up (expected: 1 / fraction of valid pairs)
 
 
-def _device(device):
-    if device is not None:
-        return torch.device(device)
-    if not torch.cuda.is_available():
-        raise RuntimeError("link-prediction evaluation needs a ROCm GPU: no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
+_device = partial(_common.device, task="link-prediction")
 
 
 def split_counts(edge_num, train_ratio, val_ratio, test_ratio):
@@ -104,15 +101,6 @@ def assemble_splits(shuffled, neg, train_ratio, val_ratio, test_ratio):
     return stack(train_pos, negs[0]), stack(val_pos, negs[2]), stack(test_pos, negs[1])
 
 
-def select_C(val_aucs):
-    """Index of the best validation AUC; the reference compares with >=, so the last of tied values wins."""
-    best, idx = 0, -1
-    for i, a in enumerate(val_aucs):
-        if a >= best:
-            best, idx = a, i
-    return idx
-
-
 def write_split(path, edges, sep):
     """One lp-data file: header from_id, to_id, label; sep = the config's file_sep."""
     pd.DataFrame(edges.cpu().numpy(), columns=['from_id', 'to_id', 'label']).to_csv(path, sep=sep, index=False)
@@ -150,8 +138,8 @@ def evaluate(embedding_prev, train, val, test, C_list, measure_list, max_iter=10
     if models:
         theta, res["report"] = _logreg.fit(E, tr, [m for m, _ in models], [C for _, C in models], tol=tol, max_iter=max_iter,
                                            hess_max=hess_max)
-        z_val = torch.cat([_logreg.scores(E, va, [m for m, _ in models[s:s + 16]], theta[s:s + 16]) for s in range(0, len(models), 16)])
-        z_test = torch.cat([_logreg.scores(E, te, [m for m, _ in models[s:s + 16]], theta[s:s + 16]) for s in range(0, len(models), 16)])
+        z_val = _logreg.scores_all(E, va, [m for m, _ in models], theta)
+        z_test = _logreg.scores_all(E, te, [m for m, _ in models], theta)
         for mi, measure in enumerate(lr_measures):
             rows = range(mi * len(C_list), (mi + 1) * len(C_list))
             aucs = [roc_auc(va.label, torch.sigmoid(z_val[r].to(torch.float64))) for r in rows]
@@ -179,10 +167,6 @@ def evaluate_window(embeddings, snapshot_edges, C_list, measure_list, train_rati
     return out
 
 
-def _read_nodes(base_path, node_file):
-    return pd.read_csv(os.path.join(base_path, node_file), names=['node'])['node'].tolist()
-
-
 class DataGenerator(object):
     """Reference DataGenerator: writes <date>_{train,val,test}.csv per snapshot file.  seed: 64-bit seed of the GPU draws; None draws
     one from np.random, so np.random.seed(...) reproduces a run."""
@@ -193,7 +177,7 @@ class DataGenerator(object):
         self.input_base_path = os.path.join(base_path, input_folder)
         self.output_base_path = os.path.join(base_path, output_folder)
         self.file_sep = file_sep
-        self.full_node_list = _read_nodes(base_path, node_file)
+        self.full_node_list = read_nodes(os.path.join(base_path, node_file))
         self.node_num = len(self.full_node_list)
         self.node2idx_dict = dict(zip(self.full_node_list, np.arange(self.node_num)))
         assert train_ratio + test_ratio + val_ratio <= 1.0
@@ -238,7 +222,7 @@ class LinkPredictor(object):
         self.output_base_path = os.path.join(base_path, output_folder)
         self.file_sep = file_sep
         self.measure_list = measure_list
-        self.full_node_list = _read_nodes(base_path, node_file)
+        self.full_node_list = read_nodes(os.path.join(base_path, node_file))
         self.C_list = C_list
         self.max_iter = max_iter
         self.tol = tol
@@ -253,18 +237,14 @@ class LinkPredictor(object):
 
     def link_prediction_all_time(self, method):
         dev = _device(self.device)
-        f_list = sorted(os.listdir(self.origin_base_path))
+
+        def read_splits(date):
+            return [self._read_split(date, p, dev) for p in ('train', 'val', 'test')]
+
         rows = []
-        for i, f_name in enumerate(f_list):
-            if i == 0:
-                continue
-            date = f_name.split('.')[0]
-            train, val, test = (self._read_split(date, p, dev) for p in ('train', 'val', 'test'))
-            pre_embedding_path = os.path.join(self.embedding_base_path, method, f_list[i - 1])
-            if not os.path.exists(pre_embedding_path):
-                continue
-            df = pd.read_csv(pre_embedding_path, sep=self.file_sep, index_col=0).loc[self.full_node_list, :]
-            E = torch.from_numpy(df.values.astype(np.float32)).to(dev)
+        for date, _, pre_embedding_path, (train, val, test) in method_snapshots(self.origin_base_path, self.embedding_base_path, method,
+                                                                               lag=1, first=read_splits):
+            E = torch.from_numpy(read_embedding(pre_embedding_path, self.file_sep, self.full_node_list, np.float32)).to(dev)
             res = evaluate(E, train, val, test, self.C_list, self.measure_list, max_iter=min(self.max_iter, 100), tol=self.tol)
             self.reports[(method, date)] = res
             rows.append([date] + [res["auc"][m] for m in self.measure_list])
@@ -296,10 +276,7 @@ def aggregate_results(base_path, lp_res_folder, start_idx, rep_num, method_list,
             cols = [m + '_' + str(i) for i in reps]
             df = pd.concat([tables[start_idx].loc[:, ['date', cols[0]]].copy()] + [tables[i].loc[:, [m + '_' + str(i)]] for i in reps[1:]],
                            axis=1)
-            df['avg'] = df.loc[:, cols].mean(axis=1)
-            df['max'] = df.loc[:, cols].max(axis=1)
-            df['min'] = df.loc[:, cols].min(axis=1)
-            df.to_csv(os.path.join(out_dir, method + '_' + m + '_record.csv'), sep=',', index=False)
+            aggregate_stats(df, cols).to_csv(os.path.join(out_dir, method + '_' + m + '_record.csv'), sep=',', index=False)
 
 
 def link_prediction(args):

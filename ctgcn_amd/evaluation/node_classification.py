@@ -16,22 +16,18 @@ over the split size.  evaluate() is the in-memory entry point for one split; eva
 """
 import os
 import time
+from functools import partial
 
 import numpy as np
 import pandas as pd
 import torch
 
-from . import _ovr
+from . import _common, _ovr
+from ._common import aggregate_stats, method_snapshots, read_embedding, read_nodes, select_C
 from ._ovr import Problem, require_cuda
-from .link_prediction import select_C
 
 
-def _device(device):
-    if device is not None:
-        return torch.device(device)
-    if not torch.cuda.is_available():
-        raise RuntimeError("node-classification evaluation needs a ROCm GPU: no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
+_device = partial(_common.device, task="node-classification")
 
 
 def split_counts(node_num, train_ratio, val_ratio, test_ratio):
@@ -157,10 +153,6 @@ def evaluate_window(embeddings, labels, C_list, rep_num=10, train_ratio=0.7, val
             "test_acc": np.array([r["test_acc"] for r in res]).reshape(shape + (-1,)), "results": res, "reports": reports}
 
 
-def _read_nodes(base_path, node_file):
-    return pd.read_csv(os.path.join(base_path, node_file), names=['node'])['node'].tolist()
-
-
 class DataGenerator(object):
     """Reference DataGenerator: <date>_{train,test,val}.csv (columns node, label) per snapshot file, drawn with the global
     np.random.shuffle, snapshot files in sorted order."""
@@ -172,7 +164,7 @@ class DataGenerator(object):
         self.output_base_path = os.path.abspath(os.path.join(base_path, output_folder))
         self.label_base_path = os.path.abspath(os.path.join(base_path, label_folder))
         self.file_sep = file_sep
-        self.full_node_list = _read_nodes(base_path, node_file)
+        self.full_node_list = read_nodes(os.path.join(base_path, node_file))
         self.node_num = len(self.full_node_list)
         self.node2idx_dict = dict(zip(self.full_node_list, np.arange(self.node_num)))
         assert train_ratio + test_ratio + val_ratio <= 1.0
@@ -211,7 +203,7 @@ class NodeClassifier(object):
         self.nodecls_base_path = os.path.abspath(os.path.join(base_path, nodeclas_folder))
         self.output_base_path = os.path.abspath(os.path.join(base_path, output_folder))
         self.file_sep = file_sep
-        self.full_node_list = _read_nodes(base_path, node_file)
+        self.full_node_list = read_nodes(os.path.join(base_path, node_file))
         label_base_path = os.path.abspath(os.path.join(base_path, label_folder))
         f_list = sorted(os.listdir(label_base_path))
         assert len(f_list) > 0
@@ -233,16 +225,14 @@ class NodeClassifier(object):
         print('method = ', method)
         dev = _device(self.device)
         K = len(self.classes)
+
+        def read_splits(date):
+            return [self._read_split(date, p) for p in ('train', 'val', 'test')]
+
         dates, embs, splits = [], [], []
-        for f_name in sorted(os.listdir(self.origin_base_path)):
-            date = f_name.split('.')[0]
-            parts = [self._read_split(date, p) for p in ('train', 'val', 'test')]
-            cur_embedding_path = os.path.join(self.embedding_base_path, method, f_name)
-            if not os.path.exists(cur_embedding_path):
-                continue
-            df = pd.read_csv(cur_embedding_path, sep=self.file_sep, index_col=0).loc[self.full_node_list]
+        for date, _, cur_embedding_path, parts in method_snapshots(self.origin_base_path, self.embedding_base_path, method, first=read_splits):
             t = len(embs)
-            embs.append(torch.from_numpy(df.values.astype(np.float32)))
+            embs.append(torch.from_numpy(read_embedding(cur_embedding_path, self.file_sep, self.full_node_list, np.float32)))
             prob = []
             for name, arr in zip(('train', 'val', 'test'), parts):
                 if arr.shape[0] and (arr[:, 1].min() < 0 or arr[:, 1].max() >= K):
@@ -284,10 +274,7 @@ def aggregate_results(base_path, nodecls_res_folder, start_idx, rep_num, method_
         output_base_path = os.path.join(base_path, nodecls_res_folder)
         os.makedirs(output_base_path, exist_ok=True)
         acc_list = ['acc_' + str(i) for i in range(start_idx, start_idx + rep_num)]
-        df_method['avg'] = df_method.loc[:, acc_list].mean(axis=1)
-        df_method['max'] = df_method.loc[:, acc_list].max(axis=1)
-        df_method['min'] = df_method.loc[:, acc_list].min(axis=1)
-        df_method.to_csv(os.path.join(output_base_path, method + '_acc_record.csv'), sep=',', index=False)
+        aggregate_stats(df_method, acc_list).to_csv(os.path.join(output_base_path, method + '_acc_record.csv'), sep=',', index=False)
 
 
 def node_classification(args):

@@ -16,6 +16,7 @@ There is no CPU fallback: without a GPU every entry point raises.
 """
 import os
 import time
+from functools import partial
 
 import numpy as np
 import pandas as pd
@@ -24,26 +25,15 @@ import torch
 
 from .. import _lib
 from .._lib import check, ptr
-from ..utils import read_edge_rows, symmetric_csr_from_rows
+from ..utils import symmetric_csr_from_rows
+from . import _common
+from ._common import method_snapshots, read_embedding, read_nodes as _read_nodes, snapshot_rows, stream as _stream
 
 EPS = 1e-6
 
 
-def _device(device=None):
-    if device is not None:
-        return torch.device(device)
-    if not torch.cuda.is_available():
-        raise RuntimeError("similarity-prediction evaluation needs a ROCm GPU: no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _require_cuda(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA (ROCm) tensor: similarity-prediction evaluation runs on the GPU, no CPU fallback" % what)
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
+_device = partial(_common.device, task="similarity-prediction")
+_require_cuda = partial(_common.require_cuda, task="similarity-prediction")
 
 
 def _check_alpha(alpha):
@@ -63,11 +53,7 @@ def graph_csr(file_path, full_node_list, sep='\t'):
     """The reference's get_sp_adj_mat(...).tocsr() of a snapshot file: scipy CSR float64 [n, n], symmetric, sorted columns.  The last
     row naming a pair sets its weight, self loops are dropped and a zero weight stores no entry.  A node missing from full_node_list
     raises ValueError."""
-    node2idx = dict(zip([str(v) for v in full_node_list], range(len(full_node_list))))
-    try:
-        src, dst, w = read_edge_rows(file_path, node2idx, sep)
-    except KeyError as e:
-        raise ValueError("%s names a node that is not in the node file: %s" % (file_path, e))
+    src, dst, w = snapshot_rows(file_path, full_node_list, sep)
     m = symmetric_csr_from_rows(src, dst, w, len(full_node_list))
     m.eliminate_zeros()
     return m
@@ -303,10 +289,6 @@ def evaluate(embedding, row_ptr, col, val, alpha=0.5, iter_num=100, lambda_1=Non
     return prediction_error(sim, embedding, date)
 
 
-def _read_nodes(node_file_path):
-    return pd.read_csv(node_file_path, names=['node'])['node'].tolist()
-
-
 class DataGenerator(object):
     """Reference DataGenerator: writes <date>_similarity.npz (scipy COO of the n x n similarity, int32 row/col, float64 data)."""
 
@@ -381,16 +363,11 @@ class SimilarityPredictor(object):
         return prediction_error(node_sim_mat, embedding_mat, date, self.device)
 
     def similarity_prediction_all_time(self, method):
-        f_list = sorted(os.listdir(self.origin_base_path))
         all_mse_list = []
-        for f_name in f_list:
-            date = f_name.split('.')[0]
-            node_sim_mat = self.load_similarity(date)
-            cur_embedding_path = os.path.join(self.embedding_base_path, method, f_name)
-            if not os.path.exists(cur_embedding_path):
-                continue
-            df_embedding = pd.read_csv(cur_embedding_path, sep=self.file_sep, index_col=0).loc[self.full_node_list]
-            all_mse_list.append(self.get_prediction_error(method, node_sim_mat, df_embedding.values, date))
+        for date, _, cur_embedding_path, node_sim_mat in method_snapshots(self.origin_base_path, self.embedding_base_path, method,
+                                                                          first=self.load_similarity):
+            embedding = read_embedding(cur_embedding_path, self.file_sep, self.full_node_list)
+            all_mse_list.append(self.get_prediction_error(method, node_sim_mat, embedding, date))
         df_output = pd.DataFrame(all_mse_list, columns=['date', 'mse'])
         print(df_output)
         df_output.to_csv(os.path.join(self.output_base_path, method + '_mse_record.csv'), sep=',', index=False)
