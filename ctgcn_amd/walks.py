@@ -52,7 +52,14 @@ class WalkPairs(object):
 def random_walk_corpus(row_ptr, col, val, walk_length, walk_time, weighted=True, seed=0, walks_per_round=10):
     """(WalkPairs, freq int64[n]) for one snapshot graph given as device CSR.  Walks are generated `walks_per_round` at a
     time; after each round the pair list is merged into the de-duplicated set (ctgcn_edges_to_csr), so memory stays
-    O(n · walks_per_round · L²) instead of O(n · walk_time · L²)."""
+    O(n · walks_per_round · L²) instead of O(n · walk_time · L²).  The corpus does not depend on walks_per_round: walk `it` of a node
+    draws from the key (seed, node, it, step) whichever round it falls in (tests/_sampling_ref.py is the host model of the draws).
+
+    Weighted picks bisect the per-row float32 prefix sums of `val`: edge k of a row is taken with probability
+    (cumw[k] - cumw[k-1]) / cumw[last].  For integer weights whose row sums stay below 2**24 every prefix sum is exact and that is
+    w_k / Σw exactly.  Outside that domain each pick probability is off by about 2**-24 of the row (absolute), which on very long
+    rows rounds light edges to probability 0: 441 of the edges of a 200 000-entry row of uniform(0, 1) weights
+    (tests/test_sampling_ref_host.py).  Weights must be >= 0 with a positive sum in every non-empty row."""
     ops._need_cuda(row_ptr, col, val)
     lib = _lib.load()
     dev = row_ptr.device
@@ -61,7 +68,7 @@ def random_walk_corpus(row_ptr, col, val, walk_length, walk_time, weighted=True,
     per_walk = (L + 1) * L // 2
     freq = torch.zeros(n, dtype=torch.int64, device=dev)
     val = val.to(torch.float32).contiguous()
-    cumw = torch.empty_like(val)
+    cumw = torch.empty(max(val.numel(), 1), dtype=torch.float32, device=dev)      # never a NULL pointer: an edgeless graph is valid
     have_src = torch.empty(0, dtype=torch.int32, device=dev)
     have_dst = torch.empty(0, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
