@@ -126,6 +126,12 @@ SIGNATURES = {
                                  _sz, _vp]),
     "ctgcn_nc_predict_f32": (_int, [_i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
                                     _vp]),
+    "ctgcn_ec_grad_f32": (_int, [_i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                                 _vp, _sz, _vp]),
+    "ctgcn_ec_hess_f32": (_int, [_i32, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                 _vp, _sz, _vp]),
+    "ctgcn_ec_predict_f32": (_int, [_i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                    _vp, _vp]),
     "ctgcn_sim_panel_cols": (_i64, [_i64, _i64]),
     "ctgcn_sim_series_workspace_bytes": (_sz, [_i64, _i64]),
     "ctgcn_sim_series": (_int, [_i64, _vp, _vp, _vp, _c.c_double, _i32, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),

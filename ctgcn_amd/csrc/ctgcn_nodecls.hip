@@ -10,6 +10,10 @@
 // No float atomics: a problem's blocks are (problem, chunk) pairs whose count is a function of that problem's row count alone, and
 // their fp64 partials are summed in chunk order by the reduce kernels.  So a problem's outputs are bit-identical across calls and do
 // not depend on which other problems share the launch.
+//
+// Edge classification (reference evaluation/edge_classification.py) runs through the same kernels with a pair table: a second index
+// array rows2 parallel to rows, the feature of entry i being E[rows[i]] ⊙ E[rows2[i]].  The product is formed while the tile is
+// staged (gather_tile<true>), so no [edges, d] matrix exists; everything after the staging is the one body both kinds share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,6 +75,8 @@ struct Table {
     const int64_t *row_start;    // [P+1]: rows / y entries of problem p
     const int64_t *block_start;  // [P+1]: chunk (pass) or part (Hessian) blocks of problem p
     const int64_t *rows;         // embedding row of each entry
+    const int64_t *rows2;        // pair tables: the entry's second embedding row (its feature is the product of the two); else null
+    int vec4;                    // pair tables: d % 4 == 0, lde % 4 == 0 and E 16-byte aligned, so rows are staged as float4
     const int32_t *y;            // class index of each entry
     const int32_t *model_start;  // [P+1]: models of problem p (the model arrays below are indexed relative to model_start[0])
     const int32_t *model_pos;    // positive class of each model
@@ -78,20 +84,69 @@ struct Table {
     const int32_t *model_flag;   // 0 fitted, 1 constant 0, 2 constant 1
 };
 
-// X [TE, DW]: row r = (E[rows[base + (i0 + r)·step]], 1, 0 ...) for i0 + r < cnt, zero otherwise.  Rows outside [0, n_emb) read as zero.
-__device__ __forceinline__ void gather_tile(float *X, int DW, int d, const int64_t *__restrict__ rows, int64_t base, int64_t step, int64_t i0,
-                                            int64_t cnt, int64_t n_emb, const float *__restrict__ E, int64_t lde)
+// X [TE, DW]: row r = (x, 1, 0 ...) for i0 + r < cnt, zero otherwise, entry e = base + (i0 + r)·step.  x = E[rows[e]], or with PAIR
+// E[rows[e]] ⊙ E[rows2[e]] (one fp32 multiply per column).  An index outside [0, n_emb) makes x zero.
+// PAIR with tb.vec4: half a wave per row, a float4 per lane; a wave's 8 rows are 4 per half, and the index loads and then the row
+// loads of both endpoints of all 4 are issued before the first LDS write.  Both PAIR paths write the same fp32 values.
+template <bool PAIR>
+__device__ __forceinline__ void gather_tile(float *X, int DW, int d, const Table &tb, int64_t base, int64_t step, int64_t i0, int64_t cnt,
+                                            int64_t n_emb, const float *__restrict__ E, int64_t lde)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t *__restrict__ rows = tb.rows;
+    if (PAIR && tb.vec4) {
+        constexpr int RW = TE / (THREADS / 64) / 2;        // rows per half wave
+        const int64_t *__restrict__ rows2 = tb.rows2;
+        const int half = lane >> 5, hl = lane & 31, NQ = DW >> 2, dq = d >> 2;
+        // every load below is unconditional (an entry past cnt reads entry i0, an index out of range reads row 0, and the value is
+        // dropped): a load under a lane condition gets a wait of its own, which would put the rows in flight one at a time
+        int64_t a[RW], b[RW];
+        bool ok[RW], valid[RW];
+#pragma unroll
+        for (int k = 0; k < RW; ++k) {
+            const int64_t i = i0 + wave * (2 * RW) + 2 * k + half;
+            ok[k] = i < cnt;
+            const int64_t e = base + (ok[k] ? i : i0) * step;
+            a[k] = rows[e];
+            b[k] = rows2[e];
+        }
+#pragma unroll
+        for (int k = 0; k < RW; ++k) {
+            valid[k] = ok[k] && a[k] >= 0 && a[k] < n_emb && b[k] >= 0 && b[k] < n_emb;
+            a[k] = valid[k] ? a[k] : 0;
+            b[k] = valid[k] ? b[k] : 0;
+        }
+        for (int q = hl; q < dq; q += 32) {
+            float4 va[RW], vb[RW];
+#pragma unroll
+            for (int k = 0; k < RW; ++k) {
+                va[k] = *reinterpret_cast<const float4 *>(E + a[k] * lde + 4 * q);
+                vb[k] = *reinterpret_cast<const float4 *>(E + b[k] * lde + 4 * q);
+            }
+#pragma unroll
+            for (int k = 0; k < RW; ++k) {
+                float4 o = make_float4(va[k].x * vb[k].x, va[k].y * vb[k].y, va[k].z * vb[k].z, va[k].w * vb[k].w);
+                if (!valid[k]) o = make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4 *>(X + (wave * (2 * RW) + 2 * k + half) * DW + 4 * q) = o;
+            }
+        }
+        if (dq + hl < NQ)                                  // the bias quad and the padding after it
+#pragma unroll
+            for (int k = 0; k < RW; ++k)
+                *reinterpret_cast<float4 *>(X + (wave * (2 * RW) + 2 * k + half) * DW + 4 * (dq + hl)) =
+                    make_float4(hl == 0 && ok[k] ? 1.f : 0.f, 0.f, 0.f, 0.f);
+        return;
+    }
     for (int r = wave; r < TE; r += THREADS / 64) {
         const int64_t i = i0 + r;
         const bool ok = i < cnt;
         const int64_t node = ok ? rows[base + i * step] : -1;
-        const bool valid = node >= 0 && node < n_emb;
+        const int64_t node2 = PAIR ? (ok ? tb.rows2[base + i * step] : -1) : 0;
+        const bool valid = node >= 0 && node < n_emb && node2 >= 0 && node2 < n_emb;
         float *out = X + r * DW;
         for (int c = lane; c < DW; c += 64) {
             float v = 0.f;
-            if (valid && c < d) v = E[node * lde + c];
+            if (valid && c < d) v = PAIR ? E[node * lde + c] * E[node2 * lde + c] : E[node * lde + c];
             else if (ok && c == d) v = 1.f;
             out[c] = v;
         }
@@ -102,7 +157,7 @@ __device__ __forceinline__ void gather_tile(float *X, int DW, int d, const int64
 //   GRAD (PREDICT false): models [g·gm, (g+1)·gm) of p; part[(b·G + g)·(gm·DW + gm) ...]: gradient [gm, DW] then loss [gm] (fp64).
 //   PREDICT: C groups [g·gpb, (g+1)·gpb) of p (gpb = gm / models per group); pred_out[(entry - row_start[0])·groups + group] and
 //   correct_out[p·groups + group] (integer atomics: exact, order-free).
-template <bool PREDICT>
+template <bool PREDICT, bool PAIR>
 __global__ __launch_bounds__(THREADS) void nc_pass_kernel(Table tb, int d, int gm, int groups, const int32_t *__restrict__ n_classes,
                                                           int64_t n_emb, const float *__restrict__ E, int64_t lde, const float *__restrict__ W,
                                                           int64_t M, double *__restrict__ part, int32_t *__restrict__ pred_out,
@@ -166,7 +221,7 @@ __global__ __launch_bounds__(THREADS) void nc_pass_kernel(Table tb, int d, int g
     for (int64_t tile = c0; tile < ntiles; tile += nch) {
         const int64_t i0 = tile * TE;
         __syncthreads();                                   // the previous tile is done with X and R (first pass: Wl, hits written)
-        gather_tile(X, DW, d, tb.rows, rs, 1, i0, n, n_emb, E, lde);
+        gather_tile<PAIR>(X, DW, d, tb, rs, 1, i0, n, n_emb, E, lde);
         __syncthreads();
         float z[8], zl[8];
 #pragma unroll
@@ -296,7 +351,7 @@ __global__ __launch_bounds__(THREADS) void nc_grad_reduce_kernel(Table tb, int d
 
 // Hessian partials: block (part b of problem p, model lm of p) over the subsample rows [c·chunk, min((c+1)·chunk, nsub)) of p, row i
 // of the subsample being entry row_start[p] + i·step.  part[(b·MM + lm)·D1² + j·D1 + k] for j <= k.  Models with a flag are skipped.
-template <int MAXB>
+template <int MAXB, bool PAIR>
 __global__ __launch_bounds__(THREADS) void nc_hess_kernel(Table tb, int d, int MM, int64_t hess_max, int64_t n_emb, const float *__restrict__ E,
                                                           int64_t lde, const float *__restrict__ W, float *__restrict__ part)
 {
@@ -325,7 +380,7 @@ __global__ __launch_bounds__(THREADS) void nc_hess_kernel(Table tb, int d, int M
 
     for (int64_t e0 = lo; e0 < hi; e0 += TE) {
         __syncthreads();
-        gather_tile(F, D4, d, tb.rows, rs, step, e0, hi, n_emb, E, lde);
+        gather_tile<PAIR>(F, D4, d, tb, rs, step, e0, hi, n_emb, E, lde);
         __syncthreads();
         const float zp = hess_row_z(F, D4, D1, w);
         if ((t & 7) == 0) {
@@ -382,6 +437,15 @@ static int check_table(const char *what, int32_t problems, int32_t d, int64_t bl
     return CTGCN_OK;
 }
 
+static int fail(int code, const char *what, const char *text)
+{
+    char buf[192];
+    snprintf(buf, sizeof(buf), "%s: %s", what, text);
+    return ctgcn_set_error_(code, buf);
+}
+
+static int can_vec4(int32_t d, const float *E, int64_t lde) { return d % 4 == 0 && lde % 4 == 0 && (reinterpret_cast<uintptr_t>(E) & 15) == 0; }
+
 extern "C" int64_t ctgcn_nc_chunks(int64_t n) { return chunks_of(n); }
 
 extern "C" int64_t ctgcn_nc_hess_parts(int64_t n, int64_t hess_max) { return hess_max < 1 ? 0 : hess_parts_of(n, hess_max); }
@@ -394,27 +458,29 @@ extern "C" size_t ctgcn_nc_grad_workspace_bytes(int64_t total_chunks, int32_t d,
     return (size_t)total_chunks * G * ((size_t)gm * wstride(d) + gm) * sizeof(double);
 }
 
-extern "C" int ctgcn_nc_grad_f32(int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *chunk_start,
-                                 int64_t total_chunks, const int64_t *rows, const int32_t *y, const int32_t *model_start,
-                                 const int32_t *model_pos, const double *model_w, const int32_t *model_flag, int64_t n_emb, const float *E,
-                                 int64_t lde, const float *W, int64_t models, double *loss_out, double *grad_out, void *workspace,
-                                 size_t workspace_bytes, void *stream)
+template <bool PAIR>
+static int grad_impl(const char *what, int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *chunk_start,
+                     int64_t total_chunks, const int64_t *rows, const int64_t *rows2, const int32_t *y, const int32_t *model_start,
+                     const int32_t *model_pos, const double *model_w, const int32_t *model_flag, int64_t n_emb, const float *E, int64_t lde,
+                     const float *W, int64_t models, double *loss_out, double *grad_out, void *workspace, size_t workspace_bytes,
+                     void *stream)
 {
-    int rc = check_table("nc_grad", problems, d, total_chunks, row_start, chunk_start, rows, y, model_start, model_flag, n_emb, E, lde, W, models);
+    int rc = check_table(what, problems, d, total_chunks, row_start, chunk_start, rows, y, model_start, model_flag, n_emb, E, lde, W, models);
     if (rc) return rc;
-    if (max_models < 1 || max_models > 0xffff * 64) return ctgcn_set_error_(CTGCN_E_INVALID, "nc_grad: bad max_models");
+    if (PAIR && !rows2) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (max_models < 1 || max_models > 0xffff * 64) return fail(CTGCN_E_INVALID, what, "bad max_models");
     if (models == 0) return CTGCN_OK;
-    if (!model_pos || !model_w || !loss_out || !grad_out || !workspace) return ctgcn_set_error_(CTGCN_E_INVALID, "nc_grad: null pointer");
+    if (!model_pos || !model_w || !loss_out || !grad_out || !workspace) return fail(CTGCN_E_INVALID, what, "null pointer");
     if (workspace_bytes < ctgcn_nc_grad_workspace_bytes(total_chunks, d, max_models))
-        return ctgcn_set_error_(CTGCN_E_WORKSPACE, "nc_grad: workspace too small");
+        return fail(CTGCN_E_WORKSPACE, what, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int gm = std::min((int)max_models, group_max(d));
     const int G = (max_models + gm - 1) / gm;
-    const Table tb{problems, row_start, chunk_start, rows, y, model_start, model_pos, model_w, model_flag};
+    const Table tb{problems, row_start, chunk_start, rows, rows2, PAIR ? can_vec4(d, E, lde) : 0, y, model_start, model_pos, model_w, model_flag};
     const size_t lds = pass_lds(d, gm);
-    if ((rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(nc_pass_kernel<false>), lds, "nodecls"))) return rc;
+    if ((rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(nc_pass_kernel<false, PAIR>), lds, "nodecls"))) return rc;
     double *part = (double *)workspace;
-    hipLaunchKernelGGL(nc_pass_kernel<false>, dim3((unsigned)total_chunks, (unsigned)G), dim3(THREADS), lds, st, tb, (int)d, gm, 0,
+    hipLaunchKernelGGL((nc_pass_kernel<false, PAIR>), dim3((unsigned)total_chunks, (unsigned)G), dim3(THREADS), lds, st, tb, (int)d, gm, 0,
                        (const int32_t *)nullptr, n_emb, E, lde, W, models, part, (int32_t *)nullptr, (unsigned long long *)nullptr);
     const int64_t nout = models * (d + 2);
     hipLaunchKernelGGL(nc_grad_reduce_kernel, dim3((unsigned)((nout + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, tb, (int)d, gm, G,
@@ -423,10 +489,63 @@ extern "C" int ctgcn_nc_grad_f32(int32_t problems, int32_t d, int32_t max_models
     return CTGCN_OK;
 }
 
+extern "C" int ctgcn_nc_grad_f32(int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *chunk_start,
+                                 int64_t total_chunks, const int64_t *rows, const int32_t *y, const int32_t *model_start,
+                                 const int32_t *model_pos, const double *model_w, const int32_t *model_flag, int64_t n_emb, const float *E,
+                                 int64_t lde, const float *W, int64_t models, double *loss_out, double *grad_out, void *workspace,
+                                 size_t workspace_bytes, void *stream)
+{
+    return grad_impl<false>("nc_grad", problems, d, max_models, row_start, chunk_start, total_chunks, rows, nullptr, y, model_start, model_pos,
+                            model_w, model_flag, n_emb, E, lde, W, models, loss_out, grad_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ctgcn_ec_grad_f32(int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *chunk_start,
+                                 int64_t total_chunks, const int64_t *rows, const int64_t *rows2, const int32_t *y,
+                                 const int32_t *model_start, const int32_t *model_pos, const double *model_w, const int32_t *model_flag,
+                                 int64_t n_emb, const float *E, int64_t lde, const float *W, int64_t models, double *loss_out,
+                                 double *grad_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return grad_impl<true>("ec_grad", problems, d, max_models, row_start, chunk_start, total_chunks, rows, rows2, y, model_start, model_pos,
+                           model_w, model_flag, n_emb, E, lde, W, models, loss_out, grad_out, workspace, workspace_bytes, stream);
+}
+
 extern "C" size_t ctgcn_nc_hess_workspace_bytes(int64_t total_parts, int32_t d, int32_t max_models)
 {
     if (total_parts < 1 || d < 1 || d > MAXD || max_models < 1) return 0;
     return (size_t)total_parts * max_models * (size_t)(d + 1) * (d + 1) * sizeof(float);
+}
+
+template <bool PAIR>
+static int hess_impl(const char *what, int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *part_start,
+                     int64_t total_parts, int64_t hess_max, const int64_t *rows, const int64_t *rows2, const int32_t *y,
+                     const int32_t *model_start, const int32_t *model_pos, const double *model_w, const int32_t *model_flag, int64_t n_emb,
+                     const float *E, int64_t lde, const float *W, int64_t models, double *hess_out, void *workspace, size_t workspace_bytes,
+                     void *stream)
+{
+    int rc = check_table(what, problems, d, total_parts, row_start, part_start, rows, y, model_start, model_flag, n_emb, E, lde, W, models);
+    if (rc) return rc;
+    if (PAIR && !rows2) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (max_models < 1 || max_models > 0xffff || hess_max < 1) return fail(CTGCN_E_INVALID, what, "bad max_models or hess_max");
+    if (models == 0) return CTGCN_OK;
+    if (!model_pos || !model_w || !hess_out || !workspace) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (workspace_bytes < ctgcn_nc_hess_workspace_bytes(total_parts, d, max_models))
+        return fail(CTGCN_E_WORKSPACE, what, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const Table tb{problems, row_start, part_start, rows, rows2, PAIR ? can_vec4(d, E, lde) : 0, y, model_start, model_pos, model_w, model_flag};
+    const int D1 = d + 1, D4 = (D1 + 3) & ~3;
+    const size_t lds = sizeof(float) * ((size_t)TE * D4 + TE);
+    float *part = (float *)workspace;
+    if (d <= 128)        // (d+1) padded to 4: at most 33 column blocks, 561 upper-triangle tiles -> 3 per thread
+        hipLaunchKernelGGL((nc_hess_kernel<3, PAIR>), dim3((unsigned)total_parts, (unsigned)max_models), dim3(THREADS), lds, st, tb, (int)d,
+                           (int)max_models, hess_max, n_emb, E, lde, W, part);
+    else                 // at most 65 column blocks, 2145 tiles -> 9 per thread
+        hipLaunchKernelGGL((nc_hess_kernel<9, PAIR>), dim3((unsigned)total_parts, (unsigned)max_models), dim3(THREADS), lds, st, tb, (int)d,
+                           (int)max_models, hess_max, n_emb, E, lde, W, part);
+    const int64_t total = models * D1 * D1;
+    hipLaunchKernelGGL(nc_hess_reduce_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, tb, (int)d,
+                       (int)max_models, (const float *)part, models, hess_out);
+    CTGCN_TRY(hipGetLastError());
+    return CTGCN_OK;
 }
 
 extern "C" int ctgcn_nc_hess_f32(int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *part_start,
@@ -435,27 +554,45 @@ extern "C" int ctgcn_nc_hess_f32(int32_t problems, int32_t d, int32_t max_models
                                  int64_t lde, const float *W, int64_t models, double *hess_out, void *workspace, size_t workspace_bytes,
                                  void *stream)
 {
-    int rc = check_table("nc_hess", problems, d, total_parts, row_start, part_start, rows, y, model_start, model_flag, n_emb, E, lde, W, models);
+    return hess_impl<false>("nc_hess", problems, d, max_models, row_start, part_start, total_parts, hess_max, rows, nullptr, y, model_start,
+                            model_pos, model_w, model_flag, n_emb, E, lde, W, models, hess_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ctgcn_ec_hess_f32(int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *part_start,
+                                 int64_t total_parts, int64_t hess_max, const int64_t *rows, const int64_t *rows2, const int32_t *y,
+                                 const int32_t *model_start, const int32_t *model_pos, const double *model_w, const int32_t *model_flag,
+                                 int64_t n_emb, const float *E, int64_t lde, const float *W, int64_t models, double *hess_out,
+                                 void *workspace, size_t workspace_bytes, void *stream)
+{
+    return hess_impl<true>("ec_hess", problems, d, max_models, row_start, part_start, total_parts, hess_max, rows, rows2, y, model_start,
+                           model_pos, model_w, model_flag, n_emb, E, lde, W, models, hess_out, workspace, workspace_bytes, stream);
+}
+
+template <bool PAIR>
+static int predict_impl(const char *what, int32_t problems, int32_t d, int32_t max_classes, int32_t groups, const int64_t *row_start,
+                        const int64_t *chunk_start, int64_t total_chunks, const int64_t *rows, const int64_t *rows2, const int32_t *y,
+                        const int32_t *n_classes, const int32_t *model_start, const int32_t *model_flag, int64_t n_emb, const float *E,
+                        int64_t lde, const float *W, int64_t models, int32_t *pred_out, int64_t *correct_out, void *stream)
+{
+    int rc = check_table(what, problems, d, total_chunks, row_start, chunk_start, rows, y, model_start, model_flag, n_emb, E, lde, W, models);
     if (rc) return rc;
-    if (max_models < 1 || max_models > 0xffff || hess_max < 1) return ctgcn_set_error_(CTGCN_E_INVALID, "nc_hess: bad max_models or hess_max");
-    if (models == 0) return CTGCN_OK;
-    if (!model_pos || !model_w || !hess_out || !workspace) return ctgcn_set_error_(CTGCN_E_INVALID, "nc_hess: null pointer");
-    if (workspace_bytes < ctgcn_nc_hess_workspace_bytes(total_parts, d, max_models))
-        return ctgcn_set_error_(CTGCN_E_WORKSPACE, "nc_hess: workspace too small");
+    if (PAIR && !rows2) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (groups < 1 || max_classes < 2) return fail(CTGCN_E_INVALID, what, "need groups >= 1 and max_classes >= 2");
+    if (max_classes > group_max(d)) return fail(CTGCN_E_UNSUPPORTED, what, "more classes than models per block");
+    if (!n_classes || !pred_out || !correct_out) return fail(CTGCN_E_INVALID, what, "null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const Table tb{problems, row_start, part_start, rows, y, model_start, model_pos, model_w, model_flag};
-    const int D1 = d + 1, D4 = (D1 + 3) & ~3;
-    const size_t lds = sizeof(float) * ((size_t)TE * D4 + TE);
-    float *part = (float *)workspace;
-    if (d <= 128)        // (d+1) padded to 4: at most 33 column blocks, 561 upper-triangle tiles -> 3 per thread
-        hipLaunchKernelGGL(nc_hess_kernel<3>, dim3((unsigned)total_parts, (unsigned)max_models), dim3(THREADS), lds, st, tb, (int)d,
-                           (int)max_models, hess_max, n_emb, E, lde, W, part);
-    else                 // at most 65 column blocks, 2145 tiles -> 9 per thread
-        hipLaunchKernelGGL(nc_hess_kernel<9>, dim3((unsigned)total_parts, (unsigned)max_models), dim3(THREADS), lds, st, tb, (int)d,
-                           (int)max_models, hess_max, n_emb, E, lde, W, part);
-    const int64_t total = models * D1 * D1;
-    hipLaunchKernelGGL(nc_hess_reduce_kernel, dim3((unsigned)((total + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, tb, (int)d,
-                       (int)max_models, (const float *)part, models, hess_out);
+    CTGCN_TRY(hipMemsetAsync(correct_out, 0, sizeof(int64_t) * problems * groups, st));
+    if (models == 0) return CTGCN_OK;
+    const int mpg = max_classes == 2 ? 1 : max_classes;
+    const int gm = std::min(group_max(d), groups * mpg);
+    const int gpb = gm / mpg;
+    const int G = (groups + gpb - 1) / gpb;
+    if (G > 0xffff) return fail(CTGCN_E_UNSUPPORTED, what, "too many C groups");
+    const Table tb{problems, row_start, chunk_start, rows, rows2, PAIR ? can_vec4(d, E, lde) : 0, y, model_start, nullptr, nullptr, model_flag};
+    const size_t lds = pass_lds(d, gm);
+    if ((rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(nc_pass_kernel<true, PAIR>), lds, "nodecls"))) return rc;
+    hipLaunchKernelGGL((nc_pass_kernel<true, PAIR>), dim3((unsigned)total_chunks, (unsigned)G), dim3(THREADS), lds, st, tb, (int)d, gm,
+                       (int)groups, n_classes, n_emb, E, lde, W, models, (double *)nullptr, pred_out, (unsigned long long *)correct_out);
     CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
 }
@@ -466,25 +603,16 @@ extern "C" int ctgcn_nc_predict_f32(int32_t problems, int32_t d, int32_t max_cla
                                     const float *E, int64_t lde, const float *W, int64_t models, int32_t *pred_out, int64_t *correct_out,
                                     void *stream)
 {
-    int rc = check_table("nc_predict", problems, d, total_chunks, row_start, chunk_start, rows, y, model_start, model_flag, n_emb, E, lde, W,
-                         models);
-    if (rc) return rc;
-    if (groups < 1 || max_classes < 2) return ctgcn_set_error_(CTGCN_E_INVALID, "nc_predict: need groups >= 1 and max_classes >= 2");
-    if (max_classes > group_max(d)) return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, "nc_predict: more classes than models per block");
-    if (!n_classes || !pred_out || !correct_out) return ctgcn_set_error_(CTGCN_E_INVALID, "nc_predict: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    CTGCN_TRY(hipMemsetAsync(correct_out, 0, sizeof(int64_t) * problems * groups, st));
-    if (models == 0) return CTGCN_OK;
-    const int mpg = max_classes == 2 ? 1 : max_classes;
-    const int gm = std::min(group_max(d), groups * mpg);
-    const int gpb = gm / mpg;
-    const int G = (groups + gpb - 1) / gpb;
-    if (G > 0xffff) return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, "nc_predict: too many C groups");
-    const Table tb{problems, row_start, chunk_start, rows, y, model_start, nullptr, nullptr, model_flag};
-    const size_t lds = pass_lds(d, gm);
-    if ((rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(nc_pass_kernel<true>), lds, "nodecls"))) return rc;
-    hipLaunchKernelGGL(nc_pass_kernel<true>, dim3((unsigned)total_chunks, (unsigned)G), dim3(THREADS), lds, st, tb, (int)d, gm, (int)groups,
-                       n_classes, n_emb, E, lde, W, models, (double *)nullptr, pred_out, (unsigned long long *)correct_out);
-    CTGCN_TRY(hipGetLastError());
-    return CTGCN_OK;
+    return predict_impl<false>("nc_predict", problems, d, max_classes, groups, row_start, chunk_start, total_chunks, rows, nullptr, y, n_classes,
+                               model_start, model_flag, n_emb, E, lde, W, models, pred_out, correct_out, stream);
+}
+
+extern "C" int ctgcn_ec_predict_f32(int32_t problems, int32_t d, int32_t max_classes, int32_t groups, const int64_t *row_start,
+                                    const int64_t *chunk_start, int64_t total_chunks, const int64_t *rows, const int64_t *rows2,
+                                    const int32_t *y, const int32_t *n_classes, const int32_t *model_start, const int32_t *model_flag,
+                                    int64_t n_emb, const float *E, int64_t lde, const float *W, int64_t models, int32_t *pred_out,
+                                    int64_t *correct_out, void *stream)
+{
+    return predict_impl<true>("ec_predict", problems, d, max_classes, groups, row_start, chunk_start, total_chunks, rows, rows2, y, n_classes,
+                              model_start, model_flag, n_emb, E, lde, W, models, pred_out, correct_out, stream);
 }

@@ -1,4 +1,4 @@
-"""What the four evaluation tasks share on the host: the GPU-or-raise helpers, the reference's file conventions (node file, embedding
+"""What the five evaluation tasks share on the host: the GPU-or-raise helpers, the reference's file conventions (node file, embedding
 files, the walk over a method's snapshots), the choice of C and the avg / max / min columns of the aggregated tables.  `task` is the
 name an error message speaks of ("link-prediction", ...)."""
 import os

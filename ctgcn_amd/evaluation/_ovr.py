@@ -1,4 +1,5 @@
-"""One-vs-rest balanced L2 logistic regressions of many node-classification problems, fitted together on the GPU (ctgcn_nodecls.hip).
+"""One-vs-rest balanced L2 logistic regressions of many node- or edge-classification problems, fitted together on the GPU
+(ctgcn_nodecls.hip).
 
 A problem is one (train rows, labels) set on the rows of one float32 embedding E [R, d] (several snapshots are passed as one stacked
 [T·N, d] view and the row index carries the snapshot offset).  For each C of the problem's C list it owns one binary model per class
@@ -9,6 +10,9 @@ rows is sklearn's _ConstantPredictor (probability 0 or 1) and is not fitted.
 fit() runs batched Newton over every model of every problem: per iteration one gradient pass and one Hessian pass over all problems
 (each row tile gathered once for all models of its problem) and one batched fp64 Cholesky, in bounded chunks of models, with a per-model
 active mask, by the driver of _newton.py.  A model stops when max |∇f| <= tol.
+
+A pair problem (edge classification) carries a second index rows2: its feature is E[rows] ⊙ E[rows2], formed by the kernels while
+they stage a tile (the ctgcn_ec_* entry points); nothing else differs, fit() included.
 """
 import warnings
 from dataclasses import dataclass
@@ -30,16 +34,45 @@ HESS_BYTES = 1 << 28          # bound on one Hessian call's partials and output
 require_cuda = partial(_common.require_cuda, task="node-classification")
 
 
+def _pair(problems):
+    """True for pair problems, False for node problems; ValueError for a mixed list."""
+    kinds = {p.rows2 is not None for p in problems}
+    if len(kinds) > 1:
+        raise ValueError("the problems of a table must all have rows2 (pair problems) or all lack it")
+    return bool(kinds and kinds.pop())
+
+
+def _cat_rows(problems, pair, task, dev):
+    """(rows, rows2 or None, y) of the problems back to back; one dummy entry when there is none (the kernels read an entry pointer)."""
+    for p in problems:
+        _common.require_cuda(p.rows, "row index", task)
+        _common.require_cuda(p.y, "labels", task)
+        if pair:
+            _common.require_cuda(p.rows2, "second row index", task)
+            if p.rows2.numel() != p.rows.numel():
+                raise ValueError("rows and rows2 of a pair problem must have the same length")
+    rows = torch.cat([p.rows.reshape(-1).to(torch.int64) for p in problems]).contiguous()
+    rows2 = torch.cat([p.rows2.reshape(-1).to(torch.int64) for p in problems]).contiguous() if pair else None
+    y = torch.cat([p.y.reshape(-1).to(torch.int32) for p in problems]).contiguous()
+    if rows.numel() == 0:
+        rows = torch.zeros(1, dtype=torch.int64, device=dev)
+        rows2 = torch.zeros(1, dtype=torch.int64, device=dev) if pair else None
+        y = torch.zeros(1, dtype=torch.int32, device=dev)
+    return rows, rows2, y
+
+
 def models_per_group(K):
     return 1 if K == 2 else K
 
 
 @dataclass
 class Problem:
-    """One split on the embedding: rows (int64 CUDA, indices into E) and y (class index in [0, K), int32 CUDA)."""
+    """One split on the embedding: rows (int64 CUDA, indices into E) and y (class index in [0, K), int32 CUDA).  With rows2 (int64 CUDA,
+    parallel to rows) the feature of an entry is E[rows] ⊙ E[rows2] instead of E[rows]."""
     rows: torch.Tensor
     y: torch.Tensor
     K: int
+    rows2: torch.Tensor = None
 
 
 @dataclass
@@ -57,6 +90,10 @@ class Table:
     """The kernels' problem table (include/ctgcn_hip.h) for a list of Problems and a shared C list, on the embedding's device."""
 
     def __init__(self, E, problems, C_list, hess_max=1 << 17):
+        self.pair = _pair(problems)
+        self.task = "edge-classification" if self.pair else "node-classification"
+        if self.pair:
+            _common.require_cuda(E, "embedding", self.task)
         _check_emb(E)
         dev = E.device
         lib = _lib.load()
@@ -66,16 +103,9 @@ class Table:
         n = [int(p.rows.numel()) for p in problems]
         self.n = n
         self.row_start_h = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
-        for p in problems:
-            require_cuda(p.rows, "row index")
-            require_cuda(p.y, "labels")
         if not problems:
             raise ValueError("no problem to fit")
-        self.rows = torch.cat([p.rows.reshape(-1).to(torch.int64) for p in problems]).contiguous()
-        self.y = torch.cat([p.y.reshape(-1).to(torch.int32) for p in problems]).contiguous()
-        if self.rows.numel() == 0:                       # the kernels read at least one entry pointer
-            self.rows = torch.zeros(1, dtype=torch.int64, device=dev)
-            self.y = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.rows, self.rows2, self.y = _cat_rows(problems, self.pair, self.task, dev)
         self.row_start = torch.from_numpy(self.row_start_h).to(dev)
         chunk_start = np.concatenate([[0], np.cumsum([lib.ctgcn_nc_chunks(k) for k in n])]).astype(np.int64)
         self.total_chunks = int(chunk_start[-1])
@@ -114,6 +144,13 @@ class Table:
         self.model_flag = torch.from_numpy(self.flags_h).to(dev)
         self.n_sub = np.array([-(-k // (-(-k // self.hess_max) if k > self.hess_max else 1)) if k else 0 for k in n], dtype=np.int64)
 
+    def _entry(self, which, rows, rows2):
+        """The C entry point of this table's kind and its index arguments: (rows,) or (rows, rows2)."""
+        lib = _lib.load()
+        if self.pair:
+            return getattr(lib, "ctgcn_ec_%s_f32" % which), (ptr(rows), ptr(rows2))
+        return getattr(lib, "ctgcn_nc_%s_f32" % which), (ptr(rows),)
+
     def loss_grad(self, theta, flags=None):
         """Σ s_i logloss (double[M]) and Σ s_i (σ - y)(x, 1) (double[M, d+1]) of every model; theta [M, d+1] fp32 or fp64."""
         lib = _lib.load()
@@ -124,10 +161,10 @@ class Table:
         ws = torch.empty(max(1, lib.ctgcn_nc_grad_workspace_bytes(total, d, self.max_models)), dtype=torch.uint8, device=E.device)
         W = _hi_lo(theta)
         flags = self.model_flag if flags is None else flags
-        check(lib.ctgcn_nc_grad_f32(self.P, d, self.max_models, ptr(self.row_start), ptr(self.chunk_start), total, ptr(self.rows),
-                                    ptr(self.y), ptr(self.model_start), ptr(self.model_pos), ptr(self.model_w), ptr(flags), E.shape[0],
-                                    ptr(E), E.stride(0), ptr(W), M, ptr(loss), ptr(grad), ptr(ws), ws.numel(), _stream()),
-              "ctgcn_nc_grad_f32")
+        fn, idx = self._entry("grad", self.rows, self.rows2)
+        check(fn(self.P, d, self.max_models, ptr(self.row_start), ptr(self.chunk_start), total, *idx, ptr(self.y), ptr(self.model_start),
+                 ptr(self.model_pos), ptr(self.model_w), ptr(flags), E.shape[0], ptr(E), E.stride(0), ptr(W), M, ptr(loss), ptr(grad),
+                 ptr(ws), ws.numel(), _stream()), fn.__name__)
         return loss, grad
 
     def hessian(self, theta, p0, p1, flags=None):
@@ -144,10 +181,10 @@ class Table:
         ws = torch.empty(max(1, lib.ctgcn_nc_hess_workspace_bytes(total, d, mm)), dtype=torch.uint8, device=E.device)
         W = theta[m0:m1].to(torch.float32).contiguous()
         flags = (self.model_flag if flags is None else flags)[m0:m1]
-        check(lib.ctgcn_nc_hess_f32(p1 - p0, d, mm, ptr(self.row_start[p0:]), ptr(part_start), total, self.hess_max, ptr(self.rows),
-                                    ptr(self.y), ptr(self.model_start[p0:]), ptr(self.model_pos[m0:]), ptr(self.model_w[m0:]),
-                                    ptr(flags), E.shape[0], ptr(E), E.stride(0), ptr(W), m1 - m0, ptr(hess), ptr(ws), ws.numel(),
-                                    _stream()), "ctgcn_nc_hess_f32")
+        fn, idx = self._entry("hess", self.rows, self.rows2)
+        check(fn(p1 - p0, d, mm, ptr(self.row_start[p0:]), ptr(part_start), total, self.hess_max, *idx, ptr(self.y),
+                 ptr(self.model_start[p0:]), ptr(self.model_pos[m0:]), ptr(self.model_w[m0:]), ptr(flags), E.shape[0], ptr(E), E.stride(0),
+                 ptr(W), m1 - m0, ptr(hess), ptr(ws), ws.numel(), _stream()), fn.__name__)
         return hess
 
     def hess_chunks(self):
@@ -173,21 +210,20 @@ class Table:
         lib = _lib.load()
         E = self.E
         n = [int(p.rows.numel()) for p in problems]
-        rows = torch.cat([p.rows.reshape(-1).to(torch.int64) for p in problems]).contiguous()
-        y = torch.cat([p.y.reshape(-1).to(torch.int32) for p in problems]).contiguous()
+        if _pair(problems) != self.pair:
+            raise ValueError("the problems to score must be of the table's kind (rows2 given or not)")
+        rows, rows2, y = _cat_rows(problems, self.pair, self.task, E.device)
         G = len(self.C_list)
-        pred = torch.empty(max(1, rows.numel()), G, dtype=torch.int32, device=E.device)
+        pred = torch.empty(max(1, sum(n)), G, dtype=torch.int32, device=E.device)
         correct = torch.empty(self.P, G, dtype=torch.int64, device=E.device)
-        if rows.numel() == 0:
-            rows = torch.zeros(1, dtype=torch.int64, device=E.device)
-            y = torch.zeros(1, dtype=torch.int32, device=E.device)
         row_start = torch.tensor(np.concatenate([[0], np.cumsum(n)]), dtype=torch.int64, device=E.device)
         chunk_h = np.concatenate([[0], np.cumsum([lib.ctgcn_nc_chunks(k) for k in n])]).astype(np.int64)
         chunk_start = torch.from_numpy(chunk_h).to(E.device)
         W = _hi_lo(theta)
-        check(lib.ctgcn_nc_predict_f32(self.P, self.d, max(self.K), G, ptr(row_start), ptr(chunk_start), int(chunk_h[-1]), ptr(rows),
-                                       ptr(y), ptr(self.n_classes), ptr(self.model_start), ptr(self.model_flag), E.shape[0], ptr(E),
-                                       E.stride(0), ptr(W), self.M, ptr(pred), ptr(correct), _stream()), "ctgcn_nc_predict_f32")
+        fn, idx = self._entry("predict", rows, rows2)
+        check(fn(self.P, self.d, max(self.K), G, ptr(row_start), ptr(chunk_start), int(chunk_h[-1]), *idx, ptr(y), ptr(self.n_classes),
+                 ptr(self.model_start), ptr(self.model_flag), E.shape[0], ptr(E), E.stride(0), ptr(W), self.M, ptr(pred), ptr(correct),
+                 _stream()), fn.__name__)
         return pred[:sum(n)], correct
 
 

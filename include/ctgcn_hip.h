@@ -719,6 +719,17 @@ int ctgcn_ridge_sse_f64(int64_t n, int32_t d, int32_t targets, int32_t folds, in
  *   the first argmax over the group's models of fp64 expit(z) (a flagged model contributes its constant; K_p = 2: class 1 iff
  *   p > 1 - p), and correct_out[p*groups + g] (int64) = the entries whose prediction equals y.  max_classes >= every K_p, at most
  *   64 (32 when d > 131), else CTGCN_E_UNSUPPORTED.
+ *
+ * Pair tables (edge classification, evaluation/edge_classification.py): ctgcn_ec_grad_f32 / ctgcn_ec_hess_f32 / ctgcn_ec_predict_f32
+ * are the three entry points above with a second index array rows2 (int64, parallel to rows) directly after rows.  The feature of
+ * entry i is then x_i = E[rows[i]] ⊙ E[rows2[i]]: one fp32 multiply per column, done while the tile is staged into LDS, so no
+ * [entries, d] matrix is ever built; x_i is zero when either index lies outside [0, n_emb).  Everything else is the node table's:
+ * the same kernels after the staging, the same return codes and argument checks (a null rows2 is CTGCN_E_INVALID), the same limit
+ * d <= 256, and the same block counts and workspace sizes (ctgcn_nc_chunks, ctgcn_nc_hess_parts, ctgcn_nc_*_workspace_bytes), which
+ * depend on a problem's row count alone; so a pair problem's outputs are bit-identical across calls and batch mates too, and equal
+ * to those of a node table over the materialised fp32 products.  When d % 4 == 0, lde % 4 == 0 and E is 16-byte aligned the rows are
+ * staged as float4 (half a wave per 512-byte row at d = 128, both endpoints of a wave's rows in flight together), else by the scalar
+ * loop; both write the same values.
  */
 int64_t ctgcn_nc_chunks(int64_t n);
 int64_t ctgcn_nc_hess_parts(int64_t n, int64_t hess_max);
@@ -735,6 +746,21 @@ int ctgcn_nc_hess_f32(int32_t problems, int32_t d, int32_t max_models, const int
                       void *stream);
 int ctgcn_nc_predict_f32(int32_t problems, int32_t d, int32_t max_classes, int32_t groups, const int64_t *row_start,
                          const int64_t *chunk_start, int64_t total_chunks, const int64_t *rows, const int32_t *y,
+                         const int32_t *n_classes, const int32_t *model_start, const int32_t *model_flag, int64_t n_emb,
+                         const float *E, int64_t lde, const float *W, int64_t models, int32_t *pred_out, int64_t *correct_out,
+                         void *stream);
+int ctgcn_ec_grad_f32(int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *chunk_start,
+                      int64_t total_chunks, const int64_t *rows, const int64_t *rows2, const int32_t *y, const int32_t *model_start,
+                      const int32_t *model_pos, const double *model_w, const int32_t *model_flag, int64_t n_emb, const float *E,
+                      int64_t lde, const float *W, int64_t models, double *loss_out, double *grad_out, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int ctgcn_ec_hess_f32(int32_t problems, int32_t d, int32_t max_models, const int64_t *row_start, const int64_t *part_start,
+                      int64_t total_parts, int64_t hess_max, const int64_t *rows, const int64_t *rows2, const int32_t *y,
+                      const int32_t *model_start, const int32_t *model_pos, const double *model_w, const int32_t *model_flag,
+                      int64_t n_emb, const float *E, int64_t lde, const float *W, int64_t models, double *hess_out, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int ctgcn_ec_predict_f32(int32_t problems, int32_t d, int32_t max_classes, int32_t groups, const int64_t *row_start,
+                         const int64_t *chunk_start, int64_t total_chunks, const int64_t *rows, const int64_t *rows2, const int32_t *y,
                          const int32_t *n_classes, const int32_t *model_start, const int32_t *model_flag, int64_t n_emb,
                          const float *E, int64_t lde, const float *W, int64_t models, int32_t *pred_out, int64_t *correct_out,
                          void *stream);
