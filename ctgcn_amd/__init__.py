@@ -8,11 +8,12 @@ preprocessing.StructureInfoGenerator.  There is no CPU fallback.
 """
 from .core_adj import CoreAdj  # noqa: F401
 from .layers import CoreDiffusion, MLP  # noqa: F401
-from .models import CDN, CGCN, CTGCN  # noqa: F401
+from .models import CDN, CGCN, CTGCN, EdgeClassifier, InnerProduct, MLPClassifier  # noqa: F401
 from .helper import DataLoader  # noqa: F401
-from .metrics import NegativeSamplingLoss, ReconstructionLoss  # noqa: F401
-from .embedding import UnsupervisedEmbedding  # noqa: F401
+from .metrics import ClassificationLoss, NegativeSamplingLoss, ReconstructionLoss, StructureClassificationLoss  # noqa: F401
+from .embedding import SupervisedEmbedding, UnsupervisedEmbedding  # noqa: F401
 from .evaluation import DataGenerator, LinkPredictor, aggregate_results, evaluate, evaluate_window, link_prediction  # noqa: F401
 
 __all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoader", "NegativeSamplingLoss", "ReconstructionLoss",
-           "UnsupervisedEmbedding", "DataGenerator", "LinkPredictor", "aggregate_results", "evaluate", "evaluate_window", "link_prediction"]
+           "UnsupervisedEmbedding", "SupervisedEmbedding", "MLPClassifier", "InnerProduct", "EdgeClassifier", "ClassificationLoss",
+           "StructureClassificationLoss", "DataGenerator", "LinkPredictor", "aggregate_results", "evaluate", "evaluate_window", "link_prediction"]

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("CTGCN_HIP_LIB") or os.path.join(_HERE, "csrc", "libct
 
 F_SELF_LOOP, F_RELU, F_NESTED = 1, 2, 4
 ACT_NONE, ACT_SELU = 0, 1
+CLS_NODE, CLS_HADAMARD, CLS_DOT = 0, 1, 2
 OP_KCORE = 1
 OP_INGEST = 2
 MAX_SLOTS = 255
@@ -144,6 +145,14 @@ SIGNATURES = {
     "ctgcn_sim_normalize": (_int, [_i64, _vp, _vp, _vp, _sz, _vp]),
     "ctgcn_sim_spearman_workspace_bytes": (_sz, [_i64]),
     "ctgcn_sim_spearman": (_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_cls_pull_piece": (_i64, []),
+    "ctgcn_cls_check_items": (_int, [_i32, _i64, _vp, _vp, _i64, _vp]),
+    "ctgcn_cls_head_fwd_f32": (_int, [_i32, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ctgcn_cls_loss_workspace_bytes": (_sz, [_i64]),
+    "ctgcn_cls_loss_f32": (_int, [_i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_cls_head_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
+    "ctgcn_cls_head_bwd_f32": (_int, [_i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                                      _vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

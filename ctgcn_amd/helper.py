@@ -130,6 +130,29 @@ class DataLoader(object):
                 out.append(torch.tensor(json.load(fp), dtype=torch.int32, device=self.device))
         return out
 
+    # ------------------------------------------------------------ supervised labels (helper.py:194-222)
+    def _label_list(self, base_path, start_idx, duration, sep, node_cols):
+        import pandas as pd
+        files = sorted(os.listdir(base_path))
+        out, seen = [], set()
+        names = ['node', 'label'] if node_cols == 1 else ['from_id', 'to_id', 'label']
+        for i in self._window(start_idx, duration):
+            df = pd.read_csv(os.path.join(base_path, files[i]), sep=sep, header=0, names=names)
+            for col in names[:node_cols]:
+                df[col] = df[col].map(lambda x: self.node2idx_dict[x])
+            seen.update(df['label'].unique().tolist())
+            out.append(torch.from_numpy(df.values.astype(np.int64)).to(self.device))
+        return out, len(seen)
+
+    def get_node_label_list(self, nlabel_base_path, start_idx, duration, sep='\t'):
+        """(per snapshot an int64 [rows, 2] tensor (node index, label) in file order, number of distinct labels over the window).
+        Files are visited in sorted() order and have a header row; node names are mapped to indices."""
+        return self._label_list(nlabel_base_path, start_idx, duration, sep, 1)
+
+    def get_edge_label_list(self, elabel_base_path, start_idx, duration, sep='\t'):
+        """(per snapshot an int64 [rows, 3] tensor (from index, to index, label) in file order, number of distinct labels)."""
+        return self._label_list(elabel_base_path, start_idx, duration, sep, 2)
+
     # --------------------------------------------------- thin plumbing kept for reference-shaped drivers
     def get_date_adj_list(self, origin_base_path, start_idx, duration, sep='\t', normalize=False, row_norm=False,
                           add_eye=False, data_type='tensor'):

@@ -6,6 +6,9 @@ the bottleneck of real training once the model is fast.  Here the draws are one 
 
 epoch_loss() of both losses is the epoch-fused path of embedding.UnsupervisedEmbedding: every batch of an epoch scored
 against ONE forward's embeddings, losses and the gradient of their sum by the kernels of ctgcn_epoch.hip.
+
+ClassificationLoss and StructureClassificationLoss are the supervised trainer's losses (reference metrics.py:169-229): cross entropy
+(or BCE with logits for 1-D scores), accuracy and ROC AUC per snapshot, by the loss pass of ctgcn_supervised.hip.
 """
 import ctypes
 import itertools
@@ -14,6 +17,7 @@ import os
 import numpy as np
 import torch
 from torch import nn
+from torch.nn import functional as F
 
 from . import _lib, ops
 from ._lib import check, ptr
@@ -249,3 +253,89 @@ class ReconstructionLoss(nn.Module):
                                                                 pge, ldge, ptr(ws), ws.numel(), ops._stream()),
                       "ctgcn_reconstruction_loss_fwd_bwd_f32")
         return losses
+
+
+class ClassificationLoss(nn.Module):
+    """(total_loss, total_acc, total_auc) of per-snapshot predictions against per-snapshot labels (reference metrics.py:169-209):
+    the loss is summed over the snapshots, accuracy and AUC are their means.
+
+    2-D predictions [items, n_class]: CrossEntropyLoss, accuracy = (first argmax == label), AUC = sklearn's micro one-vs-rest
+    roc_auc_score over the ravelled one-hot labels and softmax probabilities.  For n_class == 2 the reference's sklearn call fails
+    on the shape; here it is the binary AUC of the class-1 probability.
+    1-D predictions z (InnerProduct): BCEWithLogitsLoss, prediction z > 0 (the argmax of (1 - σ(z), σ(z)), first on ties).  The
+    reference takes its AUC of sigmoid(sigmoid(z)), whose two saturating sigmoids tie large scores in floating point; this AUC
+    ranks by z, the ranking that expression has in exact arithmetic.
+    Loss, count and probabilities come from one kernel pass (ops.cls_loss_autograd); fused=False (attribute) computes them with
+    stock torch ops.  Both take the AUC from evaluation._logreg.roc_auc on the device."""
+
+    def __init__(self, n_class):
+        super().__init__()
+        self.n_class = n_class
+        self.fused = True
+
+    def forward(self, input_list, batch_labels):
+        cls_res = input_list
+        if not isinstance(cls_res, (list, tuple)) and cls_res.dim() == 2:
+            cls_res = [cls_res]
+        return self._classification_loss(cls_res, batch_labels)
+
+    def _snapshot(self, preds, labels):
+        dot = preds.dim() == 1
+        if not dot:
+            assert preds.shape[1] == self.n_class
+        if self.fused:
+            loss, correct, prob = ops.cls_loss_autograd(preds, labels, dot=dot)
+            acc = correct[0].double() / labels.numel()
+        elif dot:
+            loss = F.binary_cross_entropy_with_logits(preds, labels.to(preds.dtype))
+            prob = torch.sigmoid(preds.detach())
+            acc = ((preds.detach() > 0).to(labels.dtype) == labels).double().sum() / labels.numel()
+        else:
+            loss = F.cross_entropy(preds, labels.long())
+            prob = torch.softmax(preds.detach(), dim=1)
+            acc = (preds.detach().max(1)[1] == labels).double().sum() / labels.numel()
+        from .evaluation._logreg import roc_auc
+        if dot:
+            auc = roc_auc(labels, preds.detach())
+        elif self.n_class == 2:
+            auc = roc_auc(labels, prob[:, 1])
+        else:
+            onehot = labels.long().unsqueeze(1) == torch.arange(self.n_class, device=labels.device).unsqueeze(0)
+            auc = roc_auc(onehot.reshape(-1), prob.reshape(-1))
+        return loss, acc, auc
+
+    def _classification_loss(self, cls_res, batch_labels):
+        total_loss, total_acc, total_auc = 0, 0, 0
+        timestamp_num = len(cls_res)
+        for i in range(timestamp_num):
+            loss_val, acc_val, auc_val = self._snapshot(cls_res[i], batch_labels[i])
+            total_loss = total_loss + loss_val
+            total_acc = total_acc + acc_val
+            total_auc = total_auc + auc_val
+        total_acc /= timestamp_num
+        total_auc /= timestamp_num
+        return total_loss, total_acc, total_auc
+
+
+class StructureClassificationLoss(nn.Module):
+    """ReconstructionLoss([embeddings, structures, None]) + ClassificationLoss for CGCN-S / CTGCN-S (reference metrics.py:214-229)."""
+
+    def __init__(self, n_class):
+        super().__init__()
+        self.reconstruction_loss = ReconstructionLoss()
+        self.classification_loss = ClassificationLoss(n_class)
+
+    @property
+    def fused(self):
+        return self.classification_loss.fused
+
+    @fused.setter
+    def fused(self, value):
+        self.classification_loss.fused = bool(value)
+
+    def forward(self, input_list, batch_labels):
+        assert len(input_list) == 3
+        cls_res, node_embedding, structure_embedding = input_list[0], input_list[1], input_list[2]
+        structure_loss = self.reconstruction_loss([node_embedding, structure_embedding, None])
+        cls_loss, total_acc, total_auc = self.classification_loss(cls_res, batch_labels)
+        return structure_loss + cls_loss, total_acc, total_auc

@@ -4,12 +4,19 @@ checkpoints depend on) and return conventions — reference models.py:8-42, 129-
 CTGCN additionally supports snapshot-parallel execution (one process per GPU, snapshots sharded over
 ranks, one all-gather of the per-snapshot hidden states right before the temporal RNN) — see
 ctgcn_amd/snapshot_parallel.py.  With no process group the behaviour is the reference's.
+
+MLPClassifier / InnerProduct / EdgeClassifier are the heads of the supervised trainer (reference models.py:46-125).  A single-Linear
+head on CUDA fp32 embeddings runs the kernels of ctgcn_supervised.hip (ops.cls_head): the gather, the Hadamard product and the
+Linear are one pass and no [items, d] matrix exists, forward or backward.
 """
 import os
 
 import torch
 from torch import nn
+from torch.nn import functional as F
 
+from . import ops
+from ._lib import ACT_NONE, ACT_SELU, CtgcnHipError
 from .layers import CoreDiffusion, MLP, rnn_reduce_norm
 from . import snapshot_parallel as sp_par
 
@@ -400,3 +407,109 @@ class CTGCN(nn.Module):
                 trans.append(tr)
         out = self.temporal_head(seq if seq is not None else _stack_steps(hx))
         return out if self.model_type == 'C' else (out, trans)
+
+
+def _snapshots(x):
+    """True for a list or a 3-D tensor of per-snapshot embeddings (CTGCN output), False for one [N, d] matrix."""
+    return isinstance(x, (list, tuple)) or x.dim() == 3
+
+
+def _check_head_input(x, what):
+    if not x.is_cuda:
+        raise CtgcnHipError("%s runs on MI355X only: got a %s tensor; there is no CPU fallback" % (what, x.device))
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError("%s reads float32 [N, d] embeddings, got %s %s" % (what, x.dtype, tuple(x.shape)))
+
+
+def _single_linear(layer_num, what):
+    if layer_num != 1:
+        raise NotImplementedError("%s: the fused head covers a single Linear (layer_num == 1, every shipped config); got layer_num = %d"
+                                  % (what, layer_num))
+
+
+class MLPClassifier(nn.Module):
+    """Node classifier head (reference models.py:46-82).  Like the reference, every snapshot goes through mlp_list[0]; the other
+    duration - 1 MLPs exist so that reference checkpoints load with strict=True.  fused=False (attribute) evaluates the reference's
+    expression with stock torch ops: x[batch_indices], Linear, SELU."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, layer_num, duration, bias=True, activate_type='N'):
+        super().__init__()
+        _single_linear(layer_num, "MLPClassifier")
+        self.input_dim, self.hidden_dim, self.output_dim = input_dim, hidden_dim, output_dim
+        self.layer_num, self.duration, self.bias, self.activate_type = layer_num, duration, bias, activate_type
+        self.fused = True
+        self.mlp_list = nn.ModuleList(MLP(input_dim, hidden_dim, output_dim, layer_num, bias=bias, activate_type=activate_type)
+                                      for _ in range(duration))
+
+    def forward(self, x, batch_indices=None):
+        if _snapshots(x):
+            return [self.mlp_classifier(x[i], None if batch_indices is None else batch_indices[i]) for i in range(len(x))]
+        return self.mlp_classifier(x, batch_indices)
+
+    def _head(self, x, idx, mode):
+        _check_head_input(x, type(self).__name__)
+        lin = self.mlp_list[0].linear
+        selu = self.activate_type == 'N'
+        if self.fused:
+            return ops.cls_head(x, idx, lin.weight, lin.bias, mode, ACT_SELU if selu else ACT_NONE)
+        feat = x[idx] if mode == ops.CLS_NODE else x[idx[0]] * x[idx[1]]
+        out = F.linear(feat, lin.weight, lin.bias)
+        return F.selu(out) if selu else out
+
+    def mlp_classifier(self, x, batch_indices=None):
+        if batch_indices is None:
+            _check_head_input(x, "MLPClassifier")
+            return self.mlp_list[0](x)
+        return self._head(x, batch_indices, ops.CLS_NODE)
+
+
+class InnerProduct(nn.Module):
+    """Edge scores <E[from], E[to]> (reduce=True, the link-prediction head) or the Hadamard matrix E[from] * E[to] (reduce=False,
+    plain torch: EdgeClassifier does not go through it).  Reference models.py:86-113."""
+
+    def __init__(self, reduce=True):
+        super().__init__()
+        self.reduce = reduce
+        self.fused = True
+
+    def forward(self, x, edge_index):
+        if _snapshots(x):
+            return [self.inner_product(x[i], edge_index[i]) for i in range(len(x))]
+        return self.inner_product(x, edge_index)
+
+    def inner_product(self, x, edge_index):
+        assert edge_index.shape[0] == 2
+        _check_head_input(x, "InnerProduct")
+        if self.reduce and self.fused:
+            return ops.cls_head(x, edge_index, None, None, ops.CLS_DOT)
+        prod = x[edge_index[0]] * x[edge_index[1]]
+        return torch.sum(prod, dim=1) if self.reduce else prod
+
+
+class EdgeClassifier(nn.Module):
+    """Edge classifier head: mlp_list[0](E[from] * E[to]) (reference models.py:116-125).  The reference's forward passes a list of
+    Hadamard matrices to a classifier that expects indices and fails for CTGCN output; this is its evident intent, per snapshot.  The
+    Hadamard matrix is never materialised on the fused path."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, layer_num, duration, bias=True, activate_type='N'):
+        super().__init__()
+        _single_linear(layer_num, "EdgeClassifier")
+        self.conv = InnerProduct(reduce=False)
+        self.classifier = MLPClassifier(input_dim, hidden_dim, output_dim, layer_num, duration, bias=bias, activate_type=activate_type)
+
+    @property
+    def fused(self):
+        return self.classifier.fused
+
+    @fused.setter
+    def fused(self, value):
+        self.classifier.fused = bool(value)
+
+    def forward(self, x, edge_index):
+        if _snapshots(x):
+            return [self._edge(x[i], edge_index[i]) for i in range(len(x))]
+        return self._edge(x, edge_index)
+
+    def _edge(self, x, edge_index):
+        assert edge_index.shape[0] == 2
+        return self.classifier._head(x, edge_index, ops.CLS_HADAMARD)

@@ -1681,3 +1681,243 @@ def gru_sequence(rnn, seq, norm, reduce_sum, out=None):
         return _gru_forward(seq.contiguous(), rnn.weight_ih_l0.detach(), rnn.weight_hh_l0.detach().contiguous(), bias, b_hn,
                             ln_w, ln_b, eps, bool(reduce_sum), out=out)
     return _GruSeq.apply(seq, rnn.weight_ih_l0, rnn.weight_hh_l0, b_ih, b_hh, ln_w, ln_b, eps, bool(reduce_sum))
+
+
+# ------------------------------------------------------------------------ supervised classifier head (ctgcn_supervised.hip)
+CLS_NODE, CLS_HADAMARD, CLS_DOT = _lib.CLS_NODE, _lib.CLS_HADAMARD, _lib.CLS_DOT
+CLS_PULL_PIECE = 512            # incidences per piece of the pull backward (ctgcn_cls_pull_piece(); checked when the library loads an item set)
+CLS_MAX_D, CLS_MAX_CLASSES = 256, 32
+
+
+class ClsIncidence(object):
+    """The incidence lists of one item set for ctgcn_cls_head_bwd_f32 (include/ctgcn_hip.h): node -> (item, other endpoint) in CSR
+    form, cut into pieces of at most `piece` incidences, every node owning at least one (possibly empty) piece."""
+
+    def __init__(self, row_ptr, inc_item, inc_other, piece_ptr, piece_node, piece_slot, hub_node, hub_slot_ptr):
+        self.row_ptr, self.inc_item, self.inc_other = row_ptr, inc_item, inc_other
+        self.piece_ptr, self.piece_node, self.piece_slot = piece_ptr, piece_node, piece_slot
+        self.hub_node, self.hub_slot_ptr = hub_node, hub_slot_ptr
+        self.n_pieces = piece_node.numel()
+        self.n_hubs = hub_node.numel()
+        self.hub_pieces = int(hub_slot_ptr[-1]) if self.n_hubs else 0
+
+
+def cls_incidence(a, b, n_nodes, piece=CLS_PULL_PIECE):
+    """ClsIncidence of the items (a[i]) (b None) or (a[i], b[i]); int64 tensors on any device, indices inside [0, n_nodes).
+    A node's list holds its incidences as first endpoint in item order, then those as second endpoint in item order (a stable
+    sort), so a pair with a == b appears twice in its node's list."""
+    dev = a.device
+    n = a.numel()
+    item = torch.arange(n, dtype=torch.int64, device=dev)
+    if b is None:
+        nodes, items, other = a, item, a
+    else:
+        nodes, items, other = torch.cat([a, b]), torch.cat([item, item]), torch.cat([b, a])
+    order = torch.sort(nodes, stable=True).indices
+    deg = torch.bincount(nodes, minlength=n_nodes)
+    row_ptr = torch.zeros(n_nodes + 1, dtype=torch.int64, device=dev)
+    row_ptr[1:] = torch.cumsum(deg, 0)
+    pieces = torch.clamp((deg + piece - 1) // piece, min=1)
+    node_piece = torch.zeros(n_nodes + 1, dtype=torch.int64, device=dev)
+    node_piece[1:] = torch.cumsum(pieces, 0)
+    piece_node = torch.repeat_interleave(torch.arange(n_nodes, dtype=torch.int64, device=dev), pieces)
+    within = torch.arange(piece_node.numel(), dtype=torch.int64, device=dev) - node_piece[piece_node]
+    piece_ptr = torch.cat([row_ptr[piece_node] + within * piece, row_ptr[-1:]])
+    hub_node = torch.nonzero(pieces > 1).flatten()
+    hub_slot_ptr = torch.zeros(hub_node.numel() + 1, dtype=torch.int64, device=dev)
+    hub_slot_ptr[1:] = torch.cumsum(pieces[hub_node], 0)
+    in_hub = (pieces > 1)[piece_node]
+    piece_slot = torch.where(in_hub, torch.cumsum(in_hub.to(torch.int64), 0) - 1, torch.full_like(piece_node, -1))
+    return ClsIncidence(row_ptr, items[order].contiguous(), other[order].contiguous(), piece_ptr.contiguous(), piece_node.contiguous(),
+                        piece_slot.contiguous(), hub_node.contiguous(), hub_slot_ptr)
+
+
+class ClsItems(object):
+    """One item set on the device: contiguous endpoint arrays, checked once against n_nodes by the library's host check, and the
+    incidence lists of the pull backward, built on first use."""
+
+    def __init__(self, idx, mode, n_nodes):
+        _need_cuda(idx)
+        idx = idx.to(torch.int64)
+        if mode == CLS_NODE:
+            if idx.dim() != 1:
+                raise ValueError("node items are a 1-D index tensor, got shape %s" % (tuple(idx.shape),))
+            self.a, self.b = idx.contiguous(), None
+        else:
+            if idx.dim() != 2 or idx.shape[0] != 2:
+                raise ValueError("pair items are a [2, items] index tensor, got shape %s" % (tuple(idx.shape),))
+            self.a, self.b = idx[0].contiguous(), idx[1].contiguous()
+        self.mode, self.n_nodes, self.items = mode, int(n_nodes), self.a.numel()
+        self._inc = None
+        lib = _lib.load()
+        if lib.ctgcn_cls_pull_piece() != CLS_PULL_PIECE:
+            raise _lib.CtgcnHipError("libctgcn_hip.so cuts pull pieces at %d, ops.CLS_PULL_PIECE is %d; rebuild"
+                                     % (lib.ctgcn_cls_pull_piece(), CLS_PULL_PIECE))
+        with torch.cuda.device(idx.device):
+            check(lib.ctgcn_cls_check_items(mode, self.items, ptr(self.a), ptr(self.b), self.n_nodes, _stream()), "ctgcn_cls_check_items")
+
+    @property
+    def incidence(self):
+        if self._inc is None:
+            self._inc = cls_incidence(self.a, self.b, self.n_nodes)
+        return self._inc
+
+
+_cls_items_cache = {}
+
+
+def cls_items(idx, mode, n_nodes):
+    """ClsItems of an index tensor, cached on the tensor's identity: the trainer passes the same index tensors every epoch.  The
+    entry keeps the tensor alive, so its id cannot be recycled while the entry exists; an in-place change is seen by _version."""
+    key = (id(idx), idx.data_ptr(), idx._version, tuple(idx.shape), int(mode), int(n_nodes))
+    hit = _cls_items_cache.get(key)
+    if hit is None:
+        if len(_cls_items_cache) > 256:
+            _cls_items_cache.clear()
+        hit = _cls_items_cache[key] = (ClsItems(idx, mode, n_nodes), idx)
+    return hit[0]
+
+
+def _cls_rows(mat, what):
+    _need_cuda(mat)
+    if mat.dim() != 2 or mat.dtype != torch.float32 or (mat.shape[1] > 1 and mat.stride(1) != 1) or (mat.shape[0] > 1 and mat.stride(0) < mat.shape[1]):
+        raise ValueError("%s must be a float32 [N, d] view with unit column stride" % what)
+    return mat.data_ptr(), max(mat.stride(0), mat.shape[1])
+
+
+def cls_head_forward(E, items, W, bias, act):
+    """logits [items, C] = act(W·f + bias) (or z [items] for CLS_DOT) of ClsItems `items` over the rows of E; no autograd."""
+    pe, lde = _cls_rows(E, "embedding")
+    if items.n_nodes != E.shape[0]:
+        raise ValueError("item set was checked against %d nodes, embedding has %d rows" % (items.n_nodes, E.shape[0]))
+    dot = items.mode == CLS_DOT
+    C = 0 if dot else W.shape[0]
+    if not dot:
+        _need_cuda(W, bias)
+        if W.dtype != torch.float32 or W.dim() != 2 or W.shape[1] != E.shape[1]:
+            raise ValueError("weight must be float32 [n_class, %d]" % E.shape[1])
+        W = W.contiguous()
+        bias = None if bias is None else bias.contiguous()
+    out = torch.empty((items.items,) if dot else (items.items, C), dtype=torch.float32, device=E.device)
+    if items.items == 0:
+        return out
+    with torch.cuda.device(E.device):
+        check(_lib.load().ctgcn_cls_head_fwd_f32(items.mode, int(act), items.items, E.shape[1], C, ptr(items.a), ptr(items.b), items.n_nodes,
+                                                 pe, lde, None if dot else ptr(W), None if dot else ptr(bias), ptr(out), _stream()),
+              "ctgcn_cls_head_fwd_f32")
+    return out
+
+
+def cls_head_backward(E, items, W, dlogits, need_dE=True, need_dW=True, need_db=True, dE=None):
+    """(dE, dW, db) of the head from dlogits (the gradient at the Linear's output).  dE has E's shape (dE: an optional buffer to fill)."""
+    pe, lde = _cls_rows(E, "embedding")
+    dot = items.mode == CLS_DOT
+    d = E.shape[1]
+    C = 1 if dot else W.shape[0]
+    dev = E.device
+    dlogits = dlogits.contiguous()
+    if dlogits.dtype != torch.float32 or dlogits.numel() != items.items * C:
+        raise ValueError("dlogits must be float32 with %d entries" % (items.items * C))
+    need_dW = need_dW and not dot
+    need_db = need_db and need_dW
+    dW = torch.empty(C, d, dtype=torch.float32, device=dev) if need_dW else None
+    db = torch.empty(C, dtype=torch.float32, device=dev) if need_db else None
+    if need_dE and dE is None:
+        dE = torch.empty_like(E)
+    if items.items == 0:
+        for t in (dE if need_dE else None, dW, db):
+            if t is not None:
+                t.zero_()
+        return (dE if need_dE else None), dW, db
+    inc = items.incidence if need_dE else None
+    pde, ldde = _cls_rows(dE, "embedding gradient") if need_dE else (None, 0)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        hub_pieces = inc.hub_pieces if inc is not None else 0
+        ws = torch.empty(max(lib.ctgcn_cls_head_bwd_workspace_bytes(items.items, d, C, hub_pieces), 16), dtype=torch.uint8, device=dev)
+        check(lib.ctgcn_cls_head_bwd_f32(items.mode, items.items, d, 0 if dot else C, ptr(items.a), ptr(items.b), items.n_nodes, pe, lde,
+                                         None if dot else ptr(W.contiguous()), ptr(dlogits),
+                                         inc.n_pieces if inc else 0, ptr(inc.piece_ptr) if inc else None, ptr(inc.piece_node) if inc else None,
+                                         ptr(inc.piece_slot) if inc else None, ptr(inc.inc_item) if inc else None,
+                                         ptr(inc.inc_other) if inc else None, inc.n_hubs if inc else 0,
+                                         ptr(inc.hub_node) if inc and inc.n_hubs else None, ptr(inc.hub_slot_ptr) if inc and inc.n_hubs else None,
+                                         hub_pieces, pde, ldde, ptr(dW), ptr(db), ptr(ws), ws.numel(), _stream()), "ctgcn_cls_head_bwd_f32")
+    return (dE if need_dE else None), dW, db
+
+
+def cls_loss(logits, labels, dot=False, act=0, want_prob=True, want_grad=True):
+    """The loss pass: (mean loss float64[1], correct int64[1], prob or None, dlogits or None).  logits [items, C] with int64 labels
+    in [0, C), or dot: logits [items] with labels in {0, 1} (BCE with logits).  act=1: dlogits also carries SELU' (see the header)."""
+    _need_cuda(logits, labels)
+    if logits.dtype != torch.float32 or logits.dim() != (1 if dot else 2):
+        raise ValueError("logits must be float32 %s" % ("[items]" if dot else "[items, n_class]"))
+    logits = logits.contiguous()
+    labels = labels.to(torch.int64).contiguous()
+    n = logits.shape[0]
+    if labels.numel() != n or n == 0:
+        raise ValueError("need one label per item and at least one item (%d labels, %d items)" % (labels.numel(), n))
+    dev = logits.device
+    loss = torch.empty(1, dtype=torch.float64, device=dev)
+    correct = torch.empty(1, dtype=torch.int64, device=dev)
+    prob = torch.empty_like(logits) if want_prob else None
+    dl = torch.empty_like(logits) if want_grad else None
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(lib.ctgcn_cls_loss_workspace_bytes(n), 16), dtype=torch.uint8, device=dev)
+        check(lib.ctgcn_cls_loss_f32(CLS_DOT if dot else CLS_NODE, int(act), n, 0 if dot else logits.shape[1], ptr(logits), ptr(labels),
+                                     ptr(loss), ptr(correct), ptr(prob), ptr(dl), ptr(ws), ws.numel(), _stream()), "ctgcn_cls_loss_f32")
+    return loss, correct, prob, dl
+
+
+_SELU_ALPHA, _SELU_SCALE = 1.6732632423543772848170429916717, 1.0507009873554804934193349852946
+
+
+class _ClsHead(torch.autograd.Function):
+    """logits of an item set from (E_t, W, bias); backward: dE in E_t's layout by the pull kernel, dW, db."""
+
+    @staticmethod
+    def forward(ctx, E, W, bias, items, act):
+        out = cls_head_forward(E.detach(), items, None if W is None else W.detach(), None if bias is None else bias.detach(), act)
+        ctx.items, ctx.act, ctx.has_bias = items, act, bias is not None
+        ctx.save_for_backward(E, W, out if act else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        E, W, out = ctx.saved_tensors
+        if ctx.act:         # SELU' from the activated output: scale where out > 0, out + scale·alpha elsewhere
+            dout = dout * torch.where(out > 0, torch.full_like(out, _SELU_SCALE), out + _SELU_SCALE * _SELU_ALPHA)
+        need_dW = W is not None and ctx.needs_input_grad[1]
+        need_db = ctx.has_bias and ctx.needs_input_grad[2]
+        dE, dW, db = cls_head_backward(E.detach(), ctx.items, None if W is None else W.detach(), dout, need_dE=ctx.needs_input_grad[0],
+                                       need_dW=need_dW or need_db, need_db=need_db)
+        return dE, (dW if need_dW else None), db, None, None
+
+
+class _ClsLoss(torch.autograd.Function):
+    """(mean loss fp32 scalar, correct int64[1], probabilities) of logits; backward: grad · dlogits from the same pass."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, dot):
+        need = logits.requires_grad
+        loss, correct, prob, dl = cls_loss(logits.detach(), labels, dot=dot, want_grad=need)
+        ctx.save_for_backward(dl)
+        ctx.mark_non_differentiable(correct, prob)
+        return loss.to(torch.float32).reshape(()), correct, prob
+
+    @staticmethod
+    def backward(ctx, gloss, _gc, _gp):
+        dl, = ctx.saved_tensors
+        return (None if dl is None else dl * gloss), None, None
+
+
+def cls_head(E, idx, W, bias, mode, act=0):
+    """Differentiable logits [items, C] (z [items] for CLS_DOT) of the items idx over the rows of E (a strided [N, d] view is read in
+    place).  idx: int64 [items] (CLS_NODE) or [2, items]; its derived tables are cached on the tensor's identity."""
+    items = cls_items(idx, mode, E.shape[0])
+    return _ClsHead.apply(E, W, bias, items, int(act))
+
+
+def cls_loss_autograd(logits, labels, dot=False):
+    """(loss, correct int64[1], prob): differentiable mean cross entropy / BCE with logits of the loss pass."""
+    return _ClsLoss.apply(logits, labels, bool(dot))

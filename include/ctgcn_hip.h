@@ -809,6 +809,54 @@ size_t ctgcn_sim_spearman_workspace_bytes(int64_t N);
 int ctgcn_sim_spearman(int64_t N, const double *xs, const int64_t *xi, const double *ys, const int64_t *yi, double *sums_out,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Classifier head of the supervised trainer (reference models.py:46-125, metrics.py:169-209; ctgcn_amd/embedding.py), ctgcn_supervised.hip.
+ * An item i is a labelled node a[i] (CTGCN_CLS_NODE, b unused) or a labelled pair (a[i], b[i]); its feature is f = E[a], f = E[a] ⊙ E[b]
+ * (CTGCN_CLS_HADAMARD, one fp32 multiply per column, formed while a tile is staged: no [items, d] array exists) or, with no head behind
+ * it, the score z = <E[a], E[b]> (CTGCN_CLS_DOT; W, bias, n_class and act are ignored).  a / b: device int64[items].  E: fp32 rows of
+ * width d at stride lde (a [T, N, d] view of [N, T, d] is read in place).  W: fp32 [n_class, d] row-major, bias: [n_class] or null.
+ * Limits: 1 <= d <= 256 and 2 <= n_class <= 32, else CTGCN_E_UNSUPPORTED.
+ *
+ * ctgcn_cls_check_items: the host check of the index arrays: copies them to the host (synchronises `stream`, launches nothing) and
+ *   returns CTGCN_E_INVALID when an index lies outside [0, n_nodes).  Index sets do not change between epochs, so a caller checks a set
+ *   once; the kernels themselves give an item with an index out of range a zero feature and never read or write outside E / dE.
+ * ctgcn_cls_head_fwd_f32: out[i, c] = act(W[c]·f_i + bias[c]), act 0 the identity ('L'), 1 SELU ('N'); DOT: out[i] = z_i.
+ * ctgcn_cls_loss_f32: over logits [items, n_class] and labels int64 in [0, n_class): mean cross entropy to loss_out (device double[1]),
+ *   the number of rows whose first maximal class is the label to correct_out (device int64[1]), softmax to prob and
+ *   dlogits = (p - onehot) / items, times SELU'(.) from the activated logits when act is 1 (so dlogits is the gradient at the Linear's
+ *   output).  DOT: logits [items], labels in {0, 1}, BCE with logits, z > 0 predicts 1, prob = σ(z), dlogits = (σ(z) - y) / items.
+ *   prob and dlogits may be null.  workspace: ctgcn_cls_loss_workspace_bytes.
+ * ctgcn_cls_head_bwd_f32: from dlogits, dE (rows at stride ldde; null: skipped) in pull form and dW [n_class, d] / db [n_class] (null:
+ *   skipped; DOT has neither).  The caller supplies the incidence lists of the item set, built once per set:
+ *     inc_item / inc_other int64[incidences]: per node, in a fixed order, the items it takes part in and the other endpoint of each
+ *       (NODE: one incidence per item, inc_other unused; pairs: two per item, a pair with a == b twice in its node's list);
+ *     pieces: every node's list cut into ceil(len / ctgcn_cls_pull_piece()) pieces, at least one (an empty one for a node with no
+ *       item, whose dE row is written as zeros), in node order: piece p is [piece_ptr[p], piece_ptr[p+1]) of node piece_node[p];
+ *     piece_slot[p]: -1 when the node has one piece (the row goes to dE), else the piece's row in the fp64 partial buffer;
+ *     hubs: the nodes with several pieces, hub_node int64[n_hubs]; their partial rows are [hub_slot_ptr[h], hub_slot_ptr[h+1]),
+ *       hub_pieces in all, added in piece order.
+ *   NODE: dE[v] = Wᵀ Σ dlogits_i; HADAMARD: Σ (Wᵀ dlogits_i) ⊙ E[other]; DOT: Σ dlogits_i E[other]; sums in list order.
+ *   workspace: ctgcn_cls_head_bwd_workspace_bytes(items, d, n_class (1 for DOT), hub_pieces).
+ * No float atomics; block and piece counts depend on the sizes alone, sums run in fp64 in a fixed order: repeated calls are bit-identical.
+ */
+#define CTGCN_CLS_NODE 0
+#define CTGCN_CLS_HADAMARD 1
+#define CTGCN_CLS_DOT 2
+int64_t ctgcn_cls_pull_piece(void);
+int ctgcn_cls_check_items(int32_t mode, int64_t items, const int64_t *a, const int64_t *b, int64_t n_nodes, void *stream);
+int ctgcn_cls_head_fwd_f32(int32_t mode, int32_t act, int64_t items, int32_t d, int32_t n_class, const int64_t *a, const int64_t *b,
+                           int64_t n_nodes, const float *E, int64_t lde, const float *W, const float *bias, float *out, void *stream);
+size_t ctgcn_cls_loss_workspace_bytes(int64_t items);
+int ctgcn_cls_loss_f32(int32_t mode, int32_t act, int64_t items, int32_t n_class, const float *logits, const int64_t *labels,
+                       double *loss_out, int64_t *correct_out, float *prob, float *dlogits, void *workspace, size_t workspace_bytes,
+                       void *stream);
+size_t ctgcn_cls_head_bwd_workspace_bytes(int64_t items, int32_t d, int32_t n_class, int64_t hub_pieces);
+int ctgcn_cls_head_bwd_f32(int32_t mode, int64_t items, int32_t d, int32_t n_class, const int64_t *a, const int64_t *b, int64_t n_nodes,
+                           const float *E, int64_t lde, const float *W, const float *dlogits, int64_t n_pieces, const int64_t *piece_ptr,
+                           const int64_t *piece_node, const int64_t *piece_slot, const int64_t *inc_item, const int64_t *inc_other,
+                           int64_t n_hubs, const int64_t *hub_node, const int64_t *hub_slot_ptr, int64_t hub_pieces, float *dE,
+                           int64_t ldde, float *dW, float *db, void *workspace, size_t workspace_bytes, void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
