@@ -578,7 +578,11 @@ static int predict_impl(const char *what, int32_t problems, int32_t d, int32_t m
     if (rc) return rc;
     if (PAIR && !rows2) return fail(CTGCN_E_INVALID, what, "null pointer");
     if (groups < 1 || max_classes < 2) return fail(CTGCN_E_INVALID, what, "need groups >= 1 and max_classes >= 2");
-    if (max_classes > group_max(d)) return fail(CTGCN_E_UNSUPPORTED, what, "more classes than models per block");
+    if (max_classes > group_max(d)) {
+        char buf[96];
+        snprintf(buf, sizeof(buf), "%d classes, at most %d at d = %d (the models of one block)", (int)max_classes, group_max(d), (int)d);
+        return fail(CTGCN_E_UNSUPPORTED, what, buf);
+    }
     if (!n_classes || !pred_out || !correct_out) return fail(CTGCN_E_INVALID, what, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     CTGCN_TRY(hipMemsetAsync(correct_out, 0, sizeof(int64_t) * problems * groups, st));

@@ -65,6 +65,11 @@ def models_per_group(K):
     return 1 if K == 2 else K
 
 
+def max_classes(d):
+    """The most classes predict() takes at width d: a C group's models share one block of the pass kernel (ctgcn_nodecls.hip)."""
+    return 64 if d <= 131 else 32
+
+
 @dataclass
 class Problem:
     """One split on the embedding: rows (int64 CUDA, indices into E) and y (class index in [0, K), int32 CUDA).  With rows2 (int64 CUDA,
@@ -212,6 +217,9 @@ class Table:
         n = [int(p.rows.numel()) for p in problems]
         if _pair(problems) != self.pair:
             raise ValueError("the problems to score must be of the table's kind (rows2 given or not)")
+        if max(self.K) > max_classes(self.d):
+            raise ValueError("%s predict: %d classes, at most %d classes at embedding width d = %d"
+                             % (self.task, max(self.K), max_classes(self.d), self.d))
         rows, rows2, y = _cat_rows(problems, self.pair, self.task, E.device)
         G = len(self.C_list)
         pred = torch.empty(max(1, sum(n)), G, dtype=torch.int32, device=E.device)

@@ -164,6 +164,22 @@ def test_nodecls_symbols_and_invalid_arguments():
     assert lib.ctgcn_nc_predict_f32(1, 200, 40, 6, p, p, 1, p, p, p, p, p, 10, p, 200, p, 240, p, p, None) == -4         # K > 32
 
 
+def test_class_limit_of_predict_is_named_and_matches_the_wrapper():
+    """predict refuses K above the models of a block (64 up to d = 131, 32 above): the C message carries the count, the limit and d,
+    and _ovr.max_classes, which Table.predict checks before any launch, is the same step function."""
+    from ctgcn_amd.evaluation import _ovr
+    lib = _lib.load()
+    p = 1     # never dereferenced: the class check comes first
+    for d in (1, 127, 128, 131, 132, 200, 256):
+        limit = _ovr.max_classes(d)
+        assert limit == (64 if d <= 131 else 32)
+        K = limit + 1
+        for fn, extra in ((lib.ctgcn_nc_predict_f32, ()), (lib.ctgcn_ec_predict_f32, (p,))):
+            assert fn(1, d, K, 2, p, p, 1, p, *extra, p, p, p, p, 10, p, d, p, 2 * K, p, p, None) == -4
+            msg = lib.ctgcn_last_error().decode()
+            assert "%d classes, at most %d at d = %d" % (K, limit, d) in msg, msg
+
+
 def test_cpu_tensors_fail_loudly():
     E = torch.zeros(6, 4)
     split = torch.tensor([[0, 0], [1, 1], [2, 0]])
