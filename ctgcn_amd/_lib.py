@@ -153,6 +153,10 @@ SIGNATURES = {
     "ctgcn_cls_head_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
     "ctgcn_cls_head_bwd_f32": (_int, [_i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_gcn_normalize_workspace_bytes": (_sz, [_i64]),
+    "ctgcn_gcn_normalize_f32": (_int, [_i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_gcn_layer_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_gcn_layer_bwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _sz, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

@@ -1,4 +1,5 @@
-"""UnsupervisedEmbedding: the reference's unsupervised trainer (reference embedding.py:13-89, 293-368) for CTGCN-C/-S and CGCN-C/-S.
+"""UnsupervisedEmbedding: the reference's unsupervised trainer (reference embedding.py:13-89, 293-368) for CTGCN-C/-S, CGCN-C/-S and the
+EvolveGCN baseline (a single-output model: trained like the -C models).
 
 The reference runs, per epoch, one full-graph forward + loss(batch) + backward for each of the ceil(N / batch_size) batches of a
 shuffled node order and steps Adam once after the last batch (gradient accumulation).  The weights do not change inside an epoch
@@ -9,7 +10,7 @@ for step.  Both modes draw the same samples: batch b of epoch e, snapshot t uses
 node order is the reference's all_nodes[torch.randperm(N)] from torch's CPU generator.
 
 SupervisedEmbedding is the reference's supervised trainer (embedding.py:93-290) for the learning types S-node, S-edge, S-link-st
-and S-link-dy on the same four models; its classifier head and loss run the kernels of ctgcn_supervised.hip.
+and S-link-dy on the same models; its classifier head and loss run the kernels of ctgcn_supervised.hip.
 """
 import math
 import os
@@ -23,7 +24,7 @@ from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLo
                       epoch_batch_seed)
 
 _S_MODELS = ('CGCN-S', 'CTGCN-S')
-_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S')
+_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN')      # EvolveGCN: single-output, trained like the -C models
 
 
 def batch_count(node_num, batch_size):

@@ -156,19 +156,43 @@ class DataLoader(object):
     # --------------------------------------------------- thin plumbing kept for reference-shaped drivers
     def get_date_adj_list(self, origin_base_path, start_idx, duration, sep='\t', normalize=False, row_norm=False,
                           add_eye=False, data_type='tensor'):
-        """Snapshot adjacency matrices (reference helper.py:27-47); core-based methods only use them to derive
-        edge lists (train.py:60-62).  Normalisation is not part of the CTGCN path and is not offered."""
+        """Snapshot adjacency matrices (reference helper.py:27-47).  Core-based methods only use them to derive edge lists
+        (train.py:60-62).  normalize=True is what the baselines take: D^-1/2 (A [+ I]) D^-1/2, or D^-1 (A [+ I]) with row_norm, as a
+        float32 sparse COO tensor on the loader's device (entries in row-major order; `_indices()` is the edge list) or, for
+        data_type='matrix', as scipy COO.  The scaling runs on the GPU (ops.gcn_normalize) instead of the reference's np.vectorize call
+        per node, so it needs has_cuda.  Two differences from the reference's float64 scipy arithmetic: the weights are cast to fp32
+        before the upload (exact for the integer weights of the shipped datasets; other weights are normalised from their fp32
+        rounding), then row sums, scales and products run in fp64 and are rounded to fp32 once; and data_type='matrix' returns those
+        fp32 values in a float64 matrix, where the reference returns the unrounded float64 one."""
         assert data_type in ['tensor', 'matrix']
-        if normalize:
-            raise NotImplementedError("normalised adjacency is only used by the reference's baselines")
         files = sorted(os.listdir(origin_base_path))
         out = []
         for i in self._window(start_idx, duration):
             mat = get_sp_adj_mat(os.path.join(origin_base_path, files[i]), self.full_node_list, sep=sep)
             if add_eye:
                 mat = (mat + sp.eye(mat.shape[0])).tocoo()
+            if normalize:
+                out.append(self._normalized(mat, row_norm, data_type))
+                continue
             out.append(_coo_tensor(mat, self.device) if data_type == 'tensor' else mat)
         return out
+
+    def _normalized(self, mat, row_norm, data_type):
+        if not self.has_cuda:
+            raise ops._lib.CtgcnHipError("the normalised adjacency is scaled by a HIP kernel: construct DataLoader(has_cuda=True); "
+                                         "there is no CPU fallback")
+        csr = sp.csr_matrix(mat)
+        csr.sort_indices()
+        if csr.nnz >= 2 ** 31:
+            raise ValueError("more than 2^31-1 stored entries")
+        row_ptr = torch.from_numpy(csr.indptr.astype(np.int32)).to(self.device)
+        col = torch.from_numpy(csr.indices.astype(np.int32)).to(self.device)
+        val = ops.gcn_normalize(row_ptr, col, torch.from_numpy(csr.data.astype(np.float32)).to(self.device), row_norm)
+        coo = csr.tocoo()
+        if data_type == 'matrix':
+            return sp.coo_matrix((val.cpu().numpy().astype(np.float64), (coo.row, coo.col)), shape=csr.shape)
+        idx = torch.from_numpy(np.vstack((coo.row, coo.col)).astype(np.int64)).to(self.device)
+        return torch.sparse_coo_tensor(idx, val, torch.Size(csr.shape))
 
     def get_degree_feature_list(self, origin_base_path, start_idx, duration, sep='\t', init_type='gaussian', std=1e-4):
         """Degree-based node features for the structural models CGCN-S / CTGCN-S (reference helper.py:109-158, called at

@@ -70,6 +70,29 @@ def as_core_adj(adj_list, device):
     return hit[0]
 
 
+_gcn_adj_cache = {}
+
+
+def as_gcn_adj(adj, device):
+    """Accept what an EvolveGCN caller passes: an ops.GcnAdj (prebuilt) or a torch sparse matrix (the loader's normalised adjacency,
+    helper.get_date_adj_list(normalize=True)).  A tensor is converted once, checked for symmetry on the device (ValueError when
+    A != A^T: the layer's backward reads the same CSR) and cached by identity."""
+    if isinstance(adj, ops.GcnAdj):
+        if adj.device != torch.device(device):
+            raise ValueError("GcnAdj on %s but features on %s" % (adj.device, device))
+        return adj
+    if not (isinstance(adj, torch.Tensor) and adj.is_sparse):
+        raise TypeError("a GcnAdj or a torch sparse matrix expected, got %s" % type(adj).__name__)
+    key = (id(adj), adj._values().data_ptr(), str(device))
+    hit = _gcn_adj_cache.get(key)
+    if hit is None:
+        if len(_gcn_adj_cache) > 256:
+            _gcn_adj_cache.clear()
+        # the entry keeps the source tensor alive, so its id cannot be recycled while the entry exists
+        hit = _gcn_adj_cache[key] = (ops.GcnAdj.from_sparse_tensor(adj, device, check_symmetric=True), adj)
+    return hit[0]
+
+
 _identity_cache = {}
 
 

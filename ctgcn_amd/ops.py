@@ -1921,3 +1921,179 @@ def cls_head(E, idx, W, bias, mode, act=0):
 def cls_loss_autograd(logits, labels, dot=False):
     """(loss, correct int64[1], prob): differentiable mean cross entropy / BCE with logits of the loss pass."""
     return _ClsLoss.apply(logits, labels, bool(dot))
+
+
+# ------------------------------------------------------------------------- GCN step of the EvolveGCN baseline (ctgcn_gcn.hip)
+GCN_ACT_NONE, GCN_ACT_RRELU = 0, 1
+GCN_PIECE_FACTOR = 4                    # a long row's piece holds 4 x long_threshold entries (ctgcn_gcn.hip)
+
+
+def gcn_normalize(row_ptr, col, val, row_norm=False):
+    """D^-1/2 A D^-1/2 (row_norm False) or D^-1 A (True) over a CSR that already holds the diagonal: the reference's
+    get_normalized_adj (utils.py:65-85) in fp64 on the GPU, rounded to fp32 once.  A negative row sum raises its ValueError."""
+    _need_cuda(row_ptr, col, val)
+    lib = _lib.load()
+    row_ptr, col = _i32(row_ptr), _i32(col)
+    val = val if (val.dtype == torch.float32 and val.is_contiguous()) else val.to(torch.float32).contiguous()
+    n = row_ptr.numel() - 1
+    dev = val.device
+    out = torch.empty_like(val)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = lib.ctgcn_gcn_normalize_workspace_bytes(n)
+        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        check(lib.ctgcn_gcn_normalize_f32(n, ptr(row_ptr), ptr(col), ptr(val), 1 if row_norm else 0, ptr(out), ptr(flag), ptr(ws), nbytes,
+                                          _stream()), "ctgcn_gcn_normalize_f32")
+    if int(flag.item()):
+        raise ValueError('invalid value encountered in power, x is negative, p is negative!')
+    return out
+
+
+class GcnAdj(object):
+    """One normalised adjacency of the GCN step as the kernels read it: int32 row_ptr / col and fp32 val of the matrix as given, plus
+    the rows longer than long_threshold entries.  The layer's backward reads the same CSR as its forward, so the matrix has to be
+    symmetric (check_symmetric=True verifies that once, on the device)."""
+    LONG_ROW = 2048
+
+    def __init__(self, row_ptr, col, val, long_threshold=None, check_symmetric=False):
+        _need_cuda(row_ptr, col, val)
+        self.row_ptr, self.col = _i32(row_ptr), _i32(col)
+        self.val = val if (val.dtype == torch.float32 and val.is_contiguous()) else val.to(torch.float32).contiguous()
+        self.n = self.row_ptr.numel() - 1
+        self.nnz = self.col.numel()
+        self.device = self.val.device
+        self.long_threshold = int(self.LONG_ROW if long_threshold is None else long_threshold)
+        if self.long_threshold < 1:
+            raise ValueError("long_threshold must be >= 1")
+        lens = self.row_ptr[1:] - self.row_ptr[:-1]
+        max_len = int(lens.max()) if self.n else 0
+        self.long_rows = None
+        self.pieces = 1
+        if max_len > self.long_threshold:
+            self.long_rows = (lens > self.long_threshold).nonzero().view(-1).to(torch.int32)
+            piece = GCN_PIECE_FACTOR * self.long_threshold
+            self.pieces = (max_len + piece - 1) // piece
+        if check_symmetric:
+            self._check_symmetric()
+        self._ws = {}
+
+    def _rows(self):
+        counts = (self.row_ptr[1:] - self.row_ptr[:-1]).to(torch.int64)
+        return torch.repeat_interleave(torch.arange(self.n, device=self.device), counts)
+
+    def _check_symmetric(self):
+        row, col = self._rows(), self.col.to(torch.int64)
+        order = torch.argsort(col * self.n + row)           # the transpose's entries in row-major order
+        key = row * self.n + col
+        same = self.nnz == 0 or bool((key == (col * self.n + row)[order]).all())
+        if same and self.nnz:
+            vt = self.val[order]
+            # r_i a r_j and r_j a r_i are each rounded once: two ulps of fp32 is as far apart as a symmetric matrix gets
+            same = bool(((self.val - vt).abs() <= 2.0 ** -22 * torch.maximum(self.val.abs(), vt.abs())).all())
+        if not same:
+            raise ValueError("gcn_layer needs a symmetric matrix (its backward reads the same CSR): A != A^T")
+
+    @classmethod
+    def from_scipy(cls, mat, device, long_threshold=None, check_symmetric=False):
+        import numpy as np
+        import scipy.sparse as sp
+        csr = sp.csr_matrix(mat)
+        csr.sum_duplicates()
+        csr.sort_indices()
+        if csr.nnz >= 2 ** 31 or csr.shape[0] >= 2 ** 31:
+            raise ValueError("more than 2^31-1 rows or stored entries")
+        return cls(torch.from_numpy(csr.indptr.astype(np.int32)).to(device), torch.from_numpy(csr.indices.astype(np.int32)).to(device),
+                   torch.from_numpy(csr.data.astype(np.float32)).to(device), long_threshold, check_symmetric)
+
+    @classmethod
+    def from_sparse_tensor(cls, t, device, long_threshold=None, check_symmetric=True):
+        if not t.is_sparse or t.dim() != 2 or t.shape[0] != t.shape[1]:
+            raise ValueError("a square torch sparse COO matrix expected")
+        t = t.to(device).coalesce()                          # row-major order, duplicates summed
+        n = t.shape[0]
+        idx = t.indices()
+        if idx.shape[1] >= 2 ** 31 or n >= 2 ** 31:
+            raise ValueError("more than 2^31-1 rows or stored entries")
+        row_ptr = torch.zeros(n + 1, dtype=torch.int64, device=idx.device)
+        row_ptr[1:] = torch.bincount(idx[0], minlength=n).cumsum(0)
+        return cls(row_ptr.to(torch.int32), idx[1].to(torch.int32), t.values().to(torch.float32), long_threshold, check_symmetric)
+
+    def to_sparse_tensor(self):
+        idx = torch.stack((self._rows(), self.col.to(torch.int64)))
+        return torch.sparse_coo_tensor(idx, self.val, torch.Size((self.n, self.n)))
+
+    def workspace(self, d):
+        """(buffer, bytes) of the long rows' partial sums for width d; one buffer per width, reused by forward and backward"""
+        if self.long_rows is None:
+            return None, 0
+        nbytes = self.long_rows.numel() * self.pieces * ((d + 3) // 4 * 4) * 4
+        ws = self._ws.get(d)
+        if ws is None:
+            ws = self._ws[d] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws, nbytes
+
+
+def _gcn_long(adj, d):
+    ws, nbytes = adj.workspace(d)
+    return ptr(adj.long_rows), 0 if adj.long_rows is None else adj.long_rows.numel(), adj.long_threshold, ptr(ws), nbytes
+
+
+def _gcn_fwd(adj, S, act, score_vec):
+    lib = _lib.load()
+    n, d = S.shape
+    Y = torch.empty(n, d, dtype=torch.float32, device=S.device)
+    scores = torch.empty(n, dtype=torch.float32, device=S.device) if score_vec is not None else None
+    with torch.cuda.device(S.device), _timed("gcn_fwd", n=n, d=d, nnz=adj.nnz):
+        check(lib.ctgcn_gcn_layer_fwd_f32(n, d, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(S), S.stride(0), ptr(Y), Y.stride(0), act,
+                                          ptr(score_vec), ptr(scores), *_gcn_long(adj, d), _stream()), "ctgcn_gcn_layer_fwd_f32")
+    return Y, scores
+
+
+def _gcn_bwd(adj, dY, Y, act):
+    lib = _lib.load()
+    n, d = dY.shape
+    dS = torch.empty(n, d, dtype=torch.float32, device=dY.device)
+    with torch.cuda.device(dY.device), _timed("gcn_bwd", n=n, d=d, nnz=adj.nnz):
+        check(lib.ctgcn_gcn_layer_bwd_f32(n, d, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(dY), dY.stride(0), ptr(Y),
+                                          0 if Y is None else Y.stride(0), act, ptr(dS), dS.stride(0), *_gcn_long(adj, d), _stream()),
+              "ctgcn_gcn_layer_bwd_f32")
+    return dS
+
+
+class _GcnLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, adj, act, score_vec):
+        Y, scores = _gcn_fwd(adj, S, act, score_vec)
+        ctx.adj, ctx.act = adj, act
+        if act:
+            ctx.save_for_backward(Y)
+        if scores is None:
+            return Y
+        ctx.mark_non_differentiable(scores)
+        return Y, scores
+
+    @staticmethod
+    def backward(ctx, dY, *_):
+        Y = ctx.saved_tensors[0] if ctx.act else None
+        dY = dY if (dY.stride(1) == 1 and dY.stride(0) >= dY.shape[1]) else dY.contiguous()
+        return _gcn_bwd(ctx.adj, dY, Y, ctx.act), None, None, None
+
+
+def gcn_layer(S, adj, act=GCN_ACT_RRELU, score_vec=None):
+    """Y = act(Â S) for a symmetric GcnAdj, differentiable in S; act 0 the identity, 1 F.rrelu as the reference calls it (eval mode,
+    slope 11/48).  With score_vec [d] also returns scores = Y · score_vec from the same pass (no gradient: a top-k selects by it)."""
+    _need_cuda(S, adj.val, score_vec)
+    if act not in (GCN_ACT_NONE, GCN_ACT_RRELU):
+        raise ValueError("act must be 0 (identity) or 1 (eval-mode RReLU)")
+    if S.dim() != 2 or S.shape[0] != adj.n:
+        raise ValueError("S must be [%d, d], got %s" % (adj.n, tuple(S.shape)))
+    if S.dtype != torch.float32:
+        raise TypeError("fp32 features expected")
+    if S.device != adj.device:
+        raise ValueError("S on %s but adjacency on %s" % (S.device, adj.device))
+    S = S if (S.stride(1) == 1 and S.stride(0) >= S.shape[1]) else S.contiguous()
+    if score_vec is not None:
+        score_vec = score_vec.detach().reshape(-1).to(torch.float32).contiguous()
+        if score_vec.numel() != S.shape[1]:
+            raise ValueError("score_vec must have %d entries" % S.shape[1])
+    return _GcnLayer.apply(S, adj, int(act), score_vec)

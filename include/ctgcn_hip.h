@@ -857,6 +857,35 @@ int ctgcn_cls_head_bwd_f32(int32_t mode, int64_t items, int32_t d, int32_t n_cla
                            int64_t n_hubs, const int64_t *hub_node, const int64_t *hub_slot_ptr, int64_t hub_pieces, float *dE,
                            int64_t ldde, float *dW, float *db, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * GCN step of the EvolveGCN baseline (reference baseline/egcn.py:74, helper.py:27-47; ctgcn_amd/baseline/egcn.py), ctgcn_gcn.hip.
+ * The matrix is an int32 CSR with fp32 values, n < 2^31 rows; the layer kernels take it as given (already normalised).
+ *
+ * ctgcn_gcn_normalize_f32: over a CSR that already holds the diagonal, val_out[e] = float(r_i · val_in[e] · (row_norm ? 1 : r_j)) with
+ *   r_i = rowsum_i^-1 (row_norm 1) or rowsum_i^-1/2 (row_norm 0), row sums, r and the product in fp64, one rounding to fp32; r_i = 0 for
+ *   a zero row sum.  *flag (device int32) is cleared by the call and set to 1 when a row sum is negative (the caller reads it and
+ *   raises).  workspace: ctgcn_gcn_normalize_workspace_bytes(n) bytes (the n scales), 8-byte aligned.
+ * ctgcn_gcn_layer_fwd_f32: Y[i] = act(Σ_e val[e] · S[col[e]]); act 0 the identity, 1 F.rrelu in eval mode (y >= 0 ? y : y · 11/48).
+ *   score_vec [d] and score_out [n], both or neither: score_out[i] = Y[i] · score_vec.
+ * ctgcn_gcn_layer_bwd_f32: dS[i] = Σ_e val[e] · (dY[col[e]] ∘ m(Y[col[e]])) over the SAME CSR (the caller guarantees a symmetric matrix);
+ *   m = 1 for act 0 (Y may be null), for act 1 m(y) = y > 0 ? 1 : 11/48, formed on the gathered row.
+ * Rows at strides lds / ldy / lddy / ldds >= d; float4 accesses when d, the strides and the pointers allow, else scalar.
+ * long_rows int32[n_long] must list exactly the rows with more than long_threshold entries (null / 0: every row is handled by its lane
+ *   group).  A long row is cut into ceil(len / (4 · long_threshold)) pieces, at most as many as the workspace holds:
+ *   workspace_bytes >= n_long · pieces · round_up(d, 4) · 4, 16-byte aligned, at least one piece per row (else CTGCN_E_WORKSPACE); with
+ *   fewer pieces than a row asks for its pieces grow.  n_long <= 65535.
+ * No atomics; every sum has a fixed order: repeated calls on the same inputs are bit-identical.
+ */
+size_t ctgcn_gcn_normalize_workspace_bytes(int64_t n);
+int ctgcn_gcn_normalize_f32(int64_t n, const int32_t *row_ptr, const int32_t *col, const float *val_in, int32_t row_norm, float *val_out,
+                            int32_t *flag, void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_gcn_layer_fwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val, const float *S, int64_t lds,
+                            float *Y, int64_t ldy, int32_t act, const float *score_vec, float *score_out, const int32_t *long_rows,
+                            int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_gcn_layer_bwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val, const float *dY,
+                            int64_t lddy, const float *Y, int64_t ldy, int32_t act, float *dS, int64_t ldds, const int32_t *long_rows,
+                            int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
