@@ -10,11 +10,20 @@
 // block-per-piece kernel: a piece is at most 4 long_threshold entries, its eight lane groups sum interleaved entries and are added in
 // group order, the pieces of a row are added in piece order by a last kernel that also finishes the row.  No atomics: every sum has a
 // fixed order, so repeated launches are bit-identical.
+//
+// The GCN step of the GCN / GCRN baselines (reference baseline/gcn.py:36-43 and :84-88, baseline/gcrn.py:56-57) is the same gather with
+// an epilogue on the finished row:
+//   conv fwd    Y[i] = epi(sum_e val[e] S[col[e]] + b); epi none, ReLU with counter-based dropout (ctgcn_rng.h), or the row's L2
+//               normalisation with the norm kept for the backward.
+//   conv prep   the backward's one N x d pass: G = d loss / d (pre-epilogue sum) from dY and Y, and the bias gradient as per-block
+//               column sums added in block order.  dS = Â^T G is then the conv forward without epilogue over the transposed CSR, so
+//               the matrix need not be symmetric and no gather reads two rows per entry.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 
+#include "ctgcn_rng.h"
 #include "ctgcn_try.h"
 
 namespace {
@@ -83,6 +92,44 @@ __device__ __forceinline__ typename vec_of<VEC>::type gather_row(const GcnArgs &
     return x;
 }
 
+// sum_e val[e] src[col[e]][foff ..] over the entries [start, end) of a row, by the row's LPR lanes: the entries are read LPR at a time
+// and handed round by shuffles, U gathered rows in flight
+template <int VEC, int LPR, bool BWD>
+__device__ __forceinline__ typename vec_of<VEC>::type row_sum(const GcnArgs &a, int start, int end, int lig, int64_t foff)
+{
+    using V = typename vec_of<VEC>::type;
+    V P = V(0.f);
+    for (int base = start; base < end; base += LPR) {
+        const int my = base + lig;
+        int c = 0;
+        float w = 0.f;
+        if (my < end) {
+            c = a.col[my];
+            w = a.val[my];
+        }
+        const int cnt = min(LPR, end - base);
+        int j = 0;
+        for (; j + U <= cnt; j += U) {
+            V xv[U];
+            float wj[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int cj = __shfl(c, j + u, LPR);
+                wj[u] = __shfl(w, j + u, LPR);
+                xv[u] = gather_row<VEC, BWD>(a, cj, foff);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) P = vfma(wj[u], xv[u], P);
+        }
+        for (; j < cnt; ++j) {
+            const int cj = __shfl(c, j, LPR);
+            const float w1 = __shfl(w, j, LPR);
+            P = vfma(w1, gather_row<VEC, BWD>(a, cj, foff), P);
+        }
+    }
+    return P;
+}
+
 template <int VEC, int LPR, bool BWD>
 __global__ __launch_bounds__(256) void gcn_row_kernel(const GcnArgs a)
 {
@@ -100,35 +147,7 @@ __global__ __launch_bounds__(256) void gcn_row_kernel(const GcnArgs a)
         const bool live = ch < a.chunks;
         // dead lanes read chunk 0 (valid memory) and never store: keeps every load unconditional
         const int64_t foff = live ? (int64_t)ch * VEC : 0;
-        V P = V(0.f);
-        for (int base = start; base < end; base += LPR) {
-            const int my = base + lig;
-            int c = 0;
-            float w = 0.f;
-            if (my < end) {
-                c = a.col[my];
-                w = a.val[my];
-            }
-            const int cnt = min(LPR, end - base);
-            int j = 0;
-            for (; j + U <= cnt; j += U) {
-                V xv[U];
-                float wj[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int cj = __shfl(c, j + u, LPR);
-                    wj[u] = __shfl(w, j + u, LPR);
-                    xv[u] = gather_row<VEC, BWD>(a, cj, foff);
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) P = vfma(wj[u], xv[u], P);
-            }
-            for (; j < cnt; ++j) {
-                const int cj = __shfl(c, j, LPR);
-                const float w1 = __shfl(w, j, LPR);
-                P = vfma(w1, gather_row<VEC, BWD>(a, cj, foff), P);
-            }
-        }
+        V P = row_sum<VEC, LPR, BWD>(a, start, end, lig, foff);
         if (!BWD && a.act) P = rrelu(P);
         if (live) {
             *(V *)(a.out + row * a.ldout + foff) = P;
@@ -200,6 +219,196 @@ __global__ __launch_bounds__(64) void gcn_final_kernel(const GcnArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ GCN / GCRN step: epilogues
+constexpr int EPI_NONE = 0, EPI_RELU = 1, EPI_L2NORM = 2;
+constexpr float L2_EPS = 1e-12f;       // F.normalize's eps: the denominator is max(norm, eps)
+
+struct ConvEpi {
+    const float *bias;      // [d] or null
+    float *norm;            // L2NORM: [n], the norm before the clamp
+    int32_t epi;
+    int32_t drop;           // RELU: p > 0
+    double p;
+    float scale;            // 1 / (1 - p)
+    uint64_t key;
+};
+
+// relu, then dropout: entry (row, c) is kept iff ctgcn_u01(key, row, c) >= p
+__device__ __forceinline__ float relu_drop(float v, const ConvEpi &e, int64_t row, int64_t c)
+{
+    if (!(v > 0.f)) return 0.f;
+    if (!e.drop) return v;
+    return ctgcn_u01(e.key, (uint64_t)row, (uint64_t)c) >= e.p ? v * e.scale : 0.f;
+}
+__device__ __forceinline__ f4 relu_drop(f4 v, const ConvEpi &e, int64_t row, int64_t c)
+{
+    return f4{relu_drop(v.x, e, row, c), relu_drop(v.y, e, row, c + 1), relu_drop(v.z, e, row, c + 2), relu_drop(v.w, e, row, c + 3)};
+}
+__device__ __forceinline__ float relu_grad(float g, float y, float scale) { return y > 0.f ? g * scale : 0.f; }
+__device__ __forceinline__ f4 relu_grad(f4 g, f4 y, float scale)
+{
+    return f4{relu_grad(g.x, y.x, scale), relu_grad(g.y, y.y, scale), relu_grad(g.z, y.z, scale), relu_grad(g.w, y.w, scale)};
+}
+
+template <int VEC, int LPR>
+__global__ __launch_bounds__(256) void gcn_conv_row_kernel(const GcnArgs a, const ConvEpi e)
+{
+    using V = typename vec_of<VEC>::type;
+    const int lig = threadIdx.x & (LPR - 1);
+    const int64_t row = (int64_t)blockIdx.x * (256 / LPR) + (threadIdx.x / LPR);
+    if (row >= a.n) return;
+    const int start = a.row_ptr[row], end = a.row_ptr[row + 1];
+    if (a.n_long > 0 && end - start > a.long_thresh) return;      // long row: gcn_piece_kernel + gcn_conv_final_kernel
+    const bool l2 = e.epi == EPI_L2NORM;
+    const bool one_pass = a.chunks <= LPR;                        // L2NORM: the row stays in registers until its norm is known
+    float ss = 0.f;
+    V P = V(0.f);
+
+    for (int p0 = 0; p0 < a.chunks; p0 += LPR) {
+        const int ch = p0 + lig;
+        const bool live = ch < a.chunks;
+        const int64_t foff = live ? (int64_t)ch * VEC : 0;
+        P = row_sum<VEC, LPR, false>(a, start, end, lig, foff);
+        if (e.bias) P += *(const V *)(e.bias + foff);
+        if (e.epi == EPI_RELU) P = relu_drop(P, e, row, foff);
+        if (l2 && live) ss += vdot(P, P);
+        if (live && !(l2 && one_pass)) *(V *)(a.out + row * a.ldout + foff) = P;
+    }
+    if (!l2) return;
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, LPR);
+    const float nrm = sqrtf(ss);
+    const float den = fmaxf(nrm, L2_EPS);
+    if (lig == 0) e.norm[row] = nrm;
+    if (one_pass) {
+        if (lig < a.chunks) *(V *)(a.out + row * a.ldout + (int64_t)lig * VEC) = P / den;
+    } else {
+        for (int ch = lig; ch < a.chunks; ch += LPR) {            // the chunks this lane wrote itself
+            V *q = (V *)(a.out + row * a.ldout + (int64_t)ch * VEC);
+            *q = *q / den;
+        }
+    }
+}
+
+// one wave per long row: the pieces in piece order, the bias, the epilogue
+__global__ __launch_bounds__(64) void gcn_conv_final_kernel(const GcnArgs a, const ConvEpi e)
+{
+    const int64_t row = a.long_rows[blockIdx.x];
+    const int len = a.row_ptr[row + 1] - a.row_ptr[row];
+    const int np = pieces_of(len, a.long_thresh, a.max_pieces);
+    const float *src = a.part + (int64_t)blockIdx.x * a.max_pieces * a.part_ld;
+    float ss = 0.f;
+    for (int c = threadIdx.x; c < a.d; c += 64) {
+        float t = src[c];
+        for (int p = 1; p < np; ++p) t += src[(int64_t)p * a.part_ld + c];
+        if (e.bias) t += e.bias[c];
+        if (e.epi == EPI_RELU) t = relu_drop(t, e, row, c);
+        ss = fmaf(t, t, ss);
+        a.out[row * a.ldout + c] = t;
+    }
+    if (e.epi != EPI_L2NORM) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    const float nrm = sqrtf(ss);
+    const float den = fmaxf(nrm, L2_EPS);
+    if (threadIdx.x == 0) e.norm[row] = nrm;
+    for (int c = threadIdx.x; c < a.d; c += 64) a.out[row * a.ldout + c] /= den;
+}
+
+// ------------------------------------------------------------------------------------------------ GCN / GCRN step: backward pre-pass
+constexpr int PREP_ROWS = 64;          // rows of a block: one partial bias-gradient vector per block
+constexpr int PREP_WAVES = 4;          // wave w takes the block's rows w, w + 4, ...; its lanes lie across the feature row
+constexpr int DB_COLS = 32, DB_SEGS = 32;
+
+struct PrepArgs {
+    int64_t n;
+    int32_t d, chunks, epi;
+    const float *dY;
+    int64_t lddy;
+    const float *Y;
+    int64_t ldy;
+    const float *norm;
+    float scale;
+    float *G;               // null: only the column sums are wanted (EPI_NONE)
+    int64_t ldg;
+    float *part;            // [blocks][part_ld] or null
+    int32_t part_ld;
+};
+
+template <int VEC>
+__global__ __launch_bounds__(64 * PREP_WAVES) void gcn_conv_prep_kernel(const PrepArgs a)
+{
+    using V = typename vec_of<VEC>::type;
+    __shared__ V sm[PREP_WAVES][64];
+    __shared__ float s_dot[PREP_ROWS], s_den[PREP_ROWS];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t row0 = (int64_t)blockIdx.x * PREP_ROWS;
+
+    if (a.epi == EPI_L2NORM) {
+        for (int k = w; k < PREP_ROWS && row0 + k < a.n; k += PREP_WAVES) {
+            const int64_t r = row0 + k;
+            float dot = 0.f;
+            for (int ch = lane; ch < a.chunks; ch += 64)
+                dot += vdot(*(const V *)(a.Y + r * a.ldy + (int64_t)ch * VEC), *(const V *)(a.dY + r * a.lddy + (int64_t)ch * VEC));
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+            if (lane == 0) {
+                const float nrm = a.norm[r];
+                const bool ok = nrm >= L2_EPS;                    // below the clamp the denominator was the constant eps
+                s_dot[k] = ok ? dot : 0.f;
+                s_den[k] = ok ? nrm : L2_EPS;
+            }
+        }
+        __syncthreads();
+    }
+    for (int p0 = 0; p0 < a.chunks; p0 += 64) {
+        const int ch = p0 + lane;
+        const bool live = ch < a.chunks;
+        const int64_t foff = (int64_t)ch * VEC;
+        V acc = V(0.f);
+        if (live) {
+            for (int k = w; k < PREP_ROWS && row0 + k < a.n; k += PREP_WAVES) {
+                const int64_t r = row0 + k;
+                V g = *(const V *)(a.dY + r * a.lddy + foff);
+                if (a.epi == EPI_RELU) g = relu_grad(g, *(const V *)(a.Y + r * a.ldy + foff), a.scale);
+                else if (a.epi == EPI_L2NORM) g = (g - *(const V *)(a.Y + r * a.ldy + foff) * s_dot[k]) / s_den[k];
+                if (a.G) *(V *)(a.G + r * a.ldg + foff) = g;
+                acc += g;
+            }
+        }
+        if (a.part) {                                             // block-uniform
+            sm[w][lane] = acc;
+            __syncthreads();
+            if (w == 0 && live) {
+                V t = sm[0][lane];
+#pragma unroll
+                for (int k = 1; k < PREP_WAVES; ++k) t += sm[k][lane];
+                *(V *)(a.part + (int64_t)blockIdx.x * a.part_ld + foff) = t;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// db[c] = sum over the pre-pass blocks of part[b][c]: DB_SEGS runs of consecutive blocks, each in block order, then the runs in run order
+__global__ __launch_bounds__(DB_COLS * DB_SEGS) void gcn_conv_db_kernel(int64_t blocks, int32_t d, int32_t part_ld, const float *part, float *db)
+{
+    __shared__ float sm[DB_SEGS][DB_COLS];
+    const int cx = threadIdx.x % DB_COLS, seg = threadIdx.x / DB_COLS;
+    const int64_t c = (int64_t)blockIdx.x * DB_COLS + cx;
+    const int64_t per = (blocks + DB_SEGS - 1) / DB_SEGS;
+    const int64_t lo = min(blocks, seg * per), hi = min(blocks, lo + per);
+    float t = 0.f;
+    if (c < d)
+        for (int64_t b = lo; b < hi; ++b) t += part[b * part_ld + c];
+    sm[seg][cx] = t;
+    __syncthreads();
+    if (seg == 0 && c < d) {
+        for (int k = 1; k < DB_SEGS; ++k) t += sm[k][cx];
+        db[c] = t;
+    }
+}
+
 int fail(int code, const char *what, const char *text)
 {
     char buf[192];
@@ -259,6 +468,32 @@ int set_common(GcnArgs &a, const char *what, int64_t n, int32_t d, const int32_t
     }
     return CTGCN_OK;
 }
+
+template <int VEC>
+int launch_conv(GcnArgs a, const ConvEpi &e, hipStream_t st)
+{
+    a.chunks = (a.d + VEC - 1) / VEC;
+    const int lpr = a.chunks <= 4 ? 4 : a.chunks <= 8 ? 8 : a.chunks <= 16 ? 16 : a.chunks <= 32 ? 32 : 64;
+    const dim3 grid((unsigned)((a.n + 256 / lpr - 1) / (256 / lpr)));
+    switch (lpr) {
+    case 4: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 4>), grid, dim3(256), 0, st, a, e); break;
+    case 8: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 8>), grid, dim3(256), 0, st, a, e); break;
+    case 16: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 16>), grid, dim3(256), 0, st, a, e); break;
+    case 32: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 32>), grid, dim3(256), 0, st, a, e); break;
+    default: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 64>), grid, dim3(256), 0, st, a, e); break;
+    }
+    CTGCN_TRY(hipGetLastError());
+    if (a.n_long > 0) {
+        hipLaunchKernelGGL((gcn_piece_kernel<VEC, false>), dim3((unsigned)a.max_pieces, (unsigned)a.n_long), dim3(PIECE_THREADS), 0, st, a);
+        CTGCN_TRY(hipGetLastError());
+        hipLaunchKernelGGL(gcn_conv_final_kernel, dim3((unsigned)a.n_long), dim3(64), 0, st, a, e);
+        CTGCN_TRY(hipGetLastError());
+    }
+    return CTGCN_OK;
+}
+
+bool bad_epi(int32_t epi) { return epi != EPI_NONE && epi != EPI_RELU && epi != EPI_L2NORM; }
+bool bad_p(double p) { return !(p >= 0.0 && p < 1.0); }
 
 // ------------------------------------------------------------------------------------------------ normalisation
 constexpr int NORM_LANES = 16;
@@ -350,4 +585,66 @@ extern "C" int ctgcn_gcn_layer_bwd_f32(int64_t n, int32_t d, const int32_t *row_
     a.src = dY; a.ldsrc = lddy; a.ymask = act ? Y : nullptr; a.ldmask = act ? ldy : 0; a.out = dS; a.ldout = ldds; a.act = act;
     const bool v4 = d % 4 == 0 && lddy % 4 == 0 && ldds % 4 == 0 && aligned16(dY) && aligned16(dS) && (!act || (ldy % 4 == 0 && aligned16(Y)));
     return v4 ? launch<4, true>(a, (hipStream_t)stream) : launch<1, true>(a, (hipStream_t)stream);
+}
+
+extern "C" int ctgcn_gcn_conv_fwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val, const float *S,
+                                      int64_t lds, const float *bias, float *Y, int64_t ldy, int32_t epi, double p, uint64_t key,
+                                      float *norm, const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace,
+                                      size_t workspace_bytes, void *stream)
+{
+    const char *what = "gcn_conv_fwd";
+    GcnArgs a{};
+    if (bad_epi(epi)) return fail(CTGCN_E_INVALID, what, "epi must be 0 (none), 1 (ReLU + dropout) or 2 (L2 row normalisation)");
+    if (bad_p(p)) return fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
+    if (lds < d || ldy < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (int rc = set_common(a, what, n, d, row_ptr, col, val, long_rows, n_long, long_threshold, workspace, workspace_bytes)) return rc;
+    if (n == 0) return CTGCN_OK;
+    if (!S || !Y || (epi == EPI_L2NORM && !norm)) return fail(CTGCN_E_INVALID, what, "null pointer");
+    a.src = S; a.ldsrc = lds; a.out = Y; a.ldout = ldy;
+    ConvEpi e{};
+    e.bias = bias; e.norm = norm; e.epi = epi; e.drop = epi == EPI_RELU && p > 0.0; e.p = p; e.scale = 1.0f / (1.0f - (float)p); e.key = key;
+    const bool v4 = d % 4 == 0 && lds % 4 == 0 && ldy % 4 == 0 && aligned16(S) && aligned16(Y) && (!bias || aligned16(bias));
+    return v4 ? launch_conv<4>(a, e, (hipStream_t)stream) : launch_conv<1>(a, e, (hipStream_t)stream);
+}
+
+extern "C" int32_t ctgcn_gcn_conv_prep_rows(void) { return PREP_ROWS; }
+
+extern "C" size_t ctgcn_gcn_conv_prep_workspace_bytes(int64_t n, int32_t d)
+{
+    if (n < 0 || d < 1) return 0;
+    return (size_t)((n + PREP_ROWS - 1) / PREP_ROWS) * (size_t)((d + 3) & ~3) * sizeof(float);
+}
+
+extern "C" int ctgcn_gcn_conv_prep_f32(int64_t n, int32_t d, const float *dY, int64_t lddy, const float *Y, int64_t ldy, const float *norm,
+                                       int32_t epi, double p, float *G, int64_t ldg, float *db, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    const char *what = "gcn_conv_prep";
+    if (n < 0 || n > INT32_MAX || d < 1) return fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
+    if (bad_epi(epi)) return fail(CTGCN_E_INVALID, what, "epi must be 0 (none), 1 (ReLU + dropout) or 2 (L2 row normalisation)");
+    if (bad_p(p)) return fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
+    if (n == 0) return CTGCN_OK;
+    const bool wants_g = epi != EPI_NONE;
+    if (!dY || (wants_g && (!Y || !G)) || (epi == EPI_L2NORM && !norm)) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (lddy < d || (wants_g && (ldy < d || ldg < d))) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (db && (!workspace || !aligned16(workspace) || workspace_bytes < ctgcn_gcn_conv_prep_workspace_bytes(n, d)))
+        return fail(CTGCN_E_WORKSPACE, what, "a bias gradient needs a 16-byte aligned workspace of ctgcn_gcn_conv_prep_workspace_bytes() bytes");
+    if (!wants_g && !db) return CTGCN_OK;                          // G = dY and no column sums: nothing to write
+    PrepArgs a{};
+    a.n = n; a.d = d; a.epi = epi; a.dY = dY; a.lddy = lddy; a.Y = wants_g ? Y : nullptr; a.ldy = ldy; a.norm = norm;
+    a.scale = epi == EPI_RELU ? 1.0f / (1.0f - (float)p) : 1.0f;
+    a.G = wants_g ? G : nullptr; a.ldg = ldg; a.part = db ? (float *)workspace : nullptr; a.part_ld = (d + 3) & ~3;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t blocks = (n + PREP_ROWS - 1) / PREP_ROWS;
+    const bool v4 = d % 4 == 0 && lddy % 4 == 0 && aligned16(dY) && (!wants_g || (ldy % 4 == 0 && ldg % 4 == 0 && aligned16(Y) && aligned16(G)));
+    a.chunks = v4 ? d / 4 : d;
+    if (v4) hipLaunchKernelGGL(gcn_conv_prep_kernel<4>, dim3((unsigned)blocks), dim3(64 * PREP_WAVES), 0, st, a);
+    else hipLaunchKernelGGL(gcn_conv_prep_kernel<1>, dim3((unsigned)blocks), dim3(64 * PREP_WAVES), 0, st, a);
+    CTGCN_TRY(hipGetLastError());
+    if (db) {
+        hipLaunchKernelGGL(gcn_conv_db_kernel, dim3((unsigned)((d + DB_COLS - 1) / DB_COLS)), dim3(DB_COLS * DB_SEGS), 0, st, blocks, d, a.part_ld,
+                           (const float *)a.part, db);
+        CTGCN_TRY(hipGetLastError());
+    }
+    return CTGCN_OK;
 }

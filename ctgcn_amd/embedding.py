@@ -1,5 +1,5 @@
 """UnsupervisedEmbedding: the reference's unsupervised trainer (reference embedding.py:13-89, 293-368) for CTGCN-C/-S, CGCN-C/-S and the
-EvolveGCN baseline (a single-output model: trained like the -C models).
+EvolveGCN and GCRN baselines (single-output models: trained like the -C models).
 
 The reference runs, per epoch, one full-graph forward + loss(batch) + backward for each of the ceil(N / batch_size) batches of a
 shuffled node order and steps Adam once after the last batch (gradient accumulation).  The weights do not change inside an epoch
@@ -24,7 +24,7 @@ from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLo
                       epoch_batch_seed)
 
 _S_MODELS = ('CGCN-S', 'CTGCN-S')
-_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN')      # EvolveGCN: single-output, trained like the -C models
+_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN')      # the baselines: single-output, trained like the -C models
 
 
 def batch_count(node_num, batch_size):

@@ -16,16 +16,17 @@ _RNN = {"GRU": nn.GRU, "LSTM": nn.LSTM}
 _RNN_MAX_ELEMS = 1 << 29     # MIOpen's RNN indexes its gate workspace with 32-bit ints: keep batch*seq*4*hidden below 2^31
 
 
-def rnn_reduce_norm(rnn, norm, seq, reduce_sum, out=None):
+def rnn_reduce_norm(rnn, norm, seq, reduce_sum, out=None, resident_backward=True):
     """norm(rnn(seq).sum(1)) or norm(rnn(seq)).  GRU(hidden=128): fused HIP kernels, forward and backward.
     LSTM(hidden=128): fused HIP recurrence for inference.  Everything else (other widths, LSTM training) goes through
-    the PyTorch-ROCm modules.  out (inference only, reduce_sum): a [rows, hidden] strided view that receives the result."""
+    the PyTorch-ROCm modules.  out (inference only, reduce_sum): a [rows, hidden] strided view that receives the result.
+    resident_backward: see ops.gru_sequence (GCRN passes False)."""
     if out is not None and torch.is_grad_enabled() and (seq.requires_grad or any(p.requires_grad for p in rnn.parameters())):
         out = None                                   # training: autograd needs its own tensors
     if ops.gru_fused_ok(rnn, seq):
         if out is not None and reduce_sum:
             return ops.gru_sequence(rnn, seq, norm, reduce_sum, out=out)
-        res = ops.gru_sequence(rnn, seq, norm, reduce_sum)
+        res = ops.gru_sequence(rnn, seq, norm, reduce_sum, resident_backward=resident_backward)
     elif ops.lstm_fused_ok(rnn, seq):
         res = ops.lstm_sequence(rnn, seq, norm, reduce_sum)
     else:
@@ -73,23 +74,24 @@ def as_core_adj(adj_list, device):
 _gcn_adj_cache = {}
 
 
-def as_gcn_adj(adj, device):
-    """Accept what an EvolveGCN caller passes: an ops.GcnAdj (prebuilt) or a torch sparse matrix (the loader's normalised adjacency,
-    helper.get_date_adj_list(normalize=True)).  A tensor is converted once, checked for symmetry on the device (ValueError when
-    A != A^T: the layer's backward reads the same CSR) and cached by identity."""
+def as_gcn_adj(adj, device, symmetric=True):
+    """Accept what an EvolveGCN / GCN caller passes: an ops.GcnAdj (prebuilt) or a torch sparse matrix (the loader's normalised
+    adjacency, helper.get_date_adj_list(normalize=True)).  A tensor is converted once and cached by identity.  symmetric=True
+    (EvolveGCN: ops.gcn_layer's backward reads the same CSR) checks A = A^T on the device and raises ValueError otherwise;
+    symmetric=False (GCN / GCRN: ops.gcn_conv, row-normalised matrices) skips the check and is cached separately."""
     if isinstance(adj, ops.GcnAdj):
         if adj.device != torch.device(device):
             raise ValueError("GcnAdj on %s but features on %s" % (adj.device, device))
         return adj
     if not (isinstance(adj, torch.Tensor) and adj.is_sparse):
         raise TypeError("a GcnAdj or a torch sparse matrix expected, got %s" % type(adj).__name__)
-    key = (id(adj), adj._values().data_ptr(), str(device))
+    key = (id(adj), adj._values().data_ptr(), str(device), bool(symmetric))
     hit = _gcn_adj_cache.get(key)
     if hit is None:
         if len(_gcn_adj_cache) > 256:
             _gcn_adj_cache.clear()
         # the entry keeps the source tensor alive, so its id cannot be recycled while the entry exists
-        hit = _gcn_adj_cache[key] = (ops.GcnAdj.from_sparse_tensor(adj, device, check_symmetric=True), adj)
+        hit = _gcn_adj_cache[key] = (ops.GcnAdj.from_sparse_tensor(adj, device, check_symmetric=bool(symmetric)), adj)
     return hit[0]
 
 

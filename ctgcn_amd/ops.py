@@ -1376,8 +1376,9 @@ class _GruSeq(torch.autograd.Function):
     and backward), runs the HIP backward recurrence and leaves the weight/input GEMMs to hipBLASLt."""
 
     @staticmethod
-    def forward(ctx, seq, w_ih, w_hh, b_ih, b_hh, ln_w, ln_b, eps, reduce_sum):
+    def forward(ctx, seq, w_ih, w_hh, b_ih, b_hh, ln_w, ln_b, eps, reduce_sum, resident_backward=True):
         hid = w_hh.shape[1]
+        ctx.resident_backward = resident_backward
         if b_ih is not None:
             bias = b_ih.detach().clone()
             bias[: 2 * hid] += b_hh.detach()[: 2 * hid]
@@ -1446,7 +1447,9 @@ class _GruSeq(torch.autograd.Function):
         split = split_mfma_enabled()
         # d_in = hidden = 128: the two resident-weight backward kernels of ctgcn_gru_bwd.hip (backward recurrence + dW_hh; dx + dW_ih) instead
         # of gru_seq_bwd_x3 + gru_dx_x3 + 2 x gru_dw_x3: d_gi is the only intermediate, dGH / dGHn never leave the CU
-        fused_bwd = split and train_fused_enabled() and forward_split_mode() == 2 and d_in == hid and steps <= 64 and w_ih_d.is_contiguous()
+        # (resident_backward=False, GCRN: the step-wise kernels below, whose sums stay at an fp32 run's error)
+        fused_bwd = ctx.resident_backward and split and train_fused_enabled() and forward_split_mode() == 2 and d_in == hid and steps <= 64 \
+            and w_ih_d.is_contiguous()
         if fused_bwd:
             nb = int(lib.ctgcn_gru_bwd_blocks(cmax))
             dw_part_ih = torch.zeros(nb, 3 * hid, hid, dtype=torch.float32, device=dev)
@@ -1542,7 +1545,7 @@ class _GruSeq(torch.autograd.Function):
         if b_ih is not None:
             db_ih = db_all[: 3 * hid].clone()
             db_hh = torch.cat([db_all[: 2 * hid], db_all[3 * hid:]])
-        return dseq, dw_ih, dw_hh, db_ih, db_hh, dln_w, (dln_b if ln_b is not None else None), None, None
+        return dseq, dw_ih, dw_hh, db_ih, db_hh, dln_w, (dln_b if ln_b is not None else None), None, None, None
 
 
 def lstm_fused_ok(rnn, seq):
@@ -1663,12 +1666,14 @@ def lstm_sequence(rnn, seq, norm, reduce_sum):
     return _LstmSeq.apply(seq, rnn.weight_ih_l0, rnn.weight_hh_l0, b_ih, b_hh, ln_w, ln_b, eps, bool(reduce_sum))
 
 
-def gru_sequence(rnn, seq, norm, reduce_sum, out=None):
+def gru_sequence(rnn, seq, norm, reduce_sum, out=None, resident_backward=True):
     """LayerNorm(sum_t GRU(seq)_t) (reduce_sum) or LayerNorm(GRU(seq)) — layers.py:59-62 / models.py:249-250.
     seq [rows, steps, d_in].  Input projection (ctgcn_gru_input_proj_f32), then the recurrence, the sum over steps and the
     LayerNorm in ONE HIP kernel (ctgcn_gru_seq_f32); with autograd enabled the backward runs ctgcn_gru_seq_bwd_f32 (see
     _GruSeq).  out (inference, reduce_sum): a [rows, hidden] view with unit column stride that receives the result,
-    e.g. column t of the temporal GRU's [rows, T, hidden] input."""
+    e.g. column t of the temporal GRU's [rows, T, hidden] input.  resident_backward=False keeps the backward off the two
+    resident-weight kernels (gru_bwd_rec / gru_bwd_in, d_in = hidden = 128, up to 64 steps) and on the step-wise HIP kernels every
+    other shape takes (ctgcn_gru_seq_bwd_f32 + the weight-gradient kernels): slower, and as accurate as an fp32 run."""
     b_ih = rnn.bias_ih_l0 if rnn.bias else None
     b_hh = rnn.bias_hh_l0 if rnn.bias else None
     ln_w = None if norm is None else norm.weight
@@ -1680,7 +1685,7 @@ def gru_sequence(rnn, seq, norm, reduce_sum, out=None):
         bias, b_hn = _gru_bias(rnn, rnn.hidden_size)
         return _gru_forward(seq.contiguous(), rnn.weight_ih_l0.detach(), rnn.weight_hh_l0.detach().contiguous(), bias, b_hn,
                             ln_w, ln_b, eps, bool(reduce_sum), out=out)
-    return _GruSeq.apply(seq, rnn.weight_ih_l0, rnn.weight_hh_l0, b_ih, b_hh, ln_w, ln_b, eps, bool(reduce_sum))
+    return _GruSeq.apply(seq, rnn.weight_ih_l0, rnn.weight_hh_l0, b_ih, b_hh, ln_w, ln_b, eps, bool(reduce_sum), bool(resident_backward))
 
 
 # ------------------------------------------------------------------------ supervised classifier head (ctgcn_supervised.hip)
@@ -1951,8 +1956,8 @@ def gcn_normalize(row_ptr, col, val, row_norm=False):
 
 class GcnAdj(object):
     """One normalised adjacency of the GCN step as the kernels read it: int32 row_ptr / col and fp32 val of the matrix as given, plus
-    the rows longer than long_threshold entries.  The layer's backward reads the same CSR as its forward, so the matrix has to be
-    symmetric (check_symmetric=True verifies that once, on the device)."""
+    the rows longer than long_threshold entries.  gcn_layer's backward reads the same CSR as its forward, so its matrix has to be
+    symmetric (check_symmetric=True verifies that once, on the device); gcn_conv's backward reads transposed(), so its need not be."""
     LONG_ROW = 2048
 
     def __init__(self, row_ptr, col, val, long_threshold=None, check_symmetric=False):
@@ -1973,9 +1978,11 @@ class GcnAdj(object):
             self.long_rows = (lens > self.long_threshold).nonzero().view(-1).to(torch.int32)
             piece = GCN_PIECE_FACTOR * self.long_threshold
             self.pieces = (max_len + piece - 1) // piece
+        self.symmetric = False                   # True once _check_symmetric has passed: the matrix is then its own transpose
         if check_symmetric:
             self._check_symmetric()
         self._ws = {}
+        self._transposed = None
 
     def _rows(self):
         counts = (self.row_ptr[1:] - self.row_ptr[:-1]).to(torch.int64)
@@ -1992,6 +1999,22 @@ class GcnAdj(object):
             same = bool(((self.val - vt).abs() <= 2.0 ** -22 * torch.maximum(self.val.abs(), vt.abs())).all())
         if not same:
             raise ValueError("gcn_layer needs a symmetric matrix (its backward reads the same CSR): A != A^T")
+        self.symmetric = True
+
+    def transposed(self):
+        """The GcnAdj of Â^T, with its own long-row list and workspaces: built once on the device by a stable sort of the entries by
+        column (the adjacency is constant over the epochs) and cached; self when the symmetry check has passed."""
+        if self.symmetric:
+            return self
+        if self._transposed is None:
+            row, col = self._rows(), self.col.to(torch.int64)
+            order = torch.argsort(col, stable=True)           # entries are in row-major order: rows stay ascending within a column
+            row_ptr = torch.zeros(self.n + 1, dtype=torch.int64, device=self.device)
+            row_ptr[1:] = torch.bincount(col, minlength=self.n).cumsum(0)
+            t = GcnAdj(row_ptr.to(torch.int32), row[order].to(torch.int32), self.val[order], self.long_threshold)
+            t._transposed = self
+            self._transposed = t
+        return self._transposed
 
     @classmethod
     def from_scipy(cls, mat, device, long_threshold=None, check_symmetric=False):
@@ -2097,3 +2120,90 @@ def gcn_layer(S, adj, act=GCN_ACT_RRELU, score_vec=None):
         if score_vec.numel() != S.shape[1]:
             raise ValueError("score_vec must have %d entries" % S.shape[1])
     return _GcnLayer.apply(S, adj, int(act), score_vec)
+
+
+# ------------------------------------------------------------------------- GCN step of the GCN / GCRN baselines (ctgcn_gcn.hip)
+GCN_EPI_NONE, GCN_EPI_RELU, GCN_EPI_L2NORM = 0, 1, 2
+
+
+def _row_view(t):
+    """t as the kernels take it: [n, d] rows with unit column stride and a row stride >= d"""
+    return t if (t.stride(1) == 1 and t.stride(0) >= t.shape[1]) else t.contiguous()
+
+
+def _gcn_conv_fwd(adj, S, bias, epi, p=0.0, key=0, out=None):
+    """(Y, norm or None): ctgcn_gcn_conv_fwd_f32; Y is out when given"""
+    lib = _lib.load()
+    n, d = S.shape
+    Y = torch.empty(n, d, dtype=torch.float32, device=S.device) if out is None else out
+    norm = torch.empty(n, dtype=torch.float32, device=S.device) if epi == GCN_EPI_L2NORM else None
+    with torch.cuda.device(S.device), _timed("gcn_conv_fwd", n=n, d=d, nnz=adj.nnz):
+        check(lib.ctgcn_gcn_conv_fwd_f32(n, d, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(S), S.stride(0), ptr(bias), ptr(Y), Y.stride(0),
+                                         epi, p, key, ptr(norm), *_gcn_long(adj, d), _stream()), "ctgcn_gcn_conv_fwd_f32")
+    return Y, norm
+
+
+def _gcn_conv_prep(dY, Y, norm, epi, p=0.0, want_db=False):
+    """(G, db): ctgcn_gcn_conv_prep_f32.  G is dY itself for GCN_EPI_NONE; db None unless wanted."""
+    lib = _lib.load()
+    n, d = dY.shape
+    dev = dY.device
+    G = torch.empty(n, d, dtype=torch.float32, device=dev) if epi != GCN_EPI_NONE else None
+    db = torch.zeros(d, dtype=torch.float32, device=dev) if want_db else None
+    nbytes = int(lib.ctgcn_gcn_conv_prep_workspace_bytes(n, d)) if want_db else 0
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if want_db else None
+    with torch.cuda.device(dev), _timed("gcn_conv_prep", n=n, d=d):
+        check(lib.ctgcn_gcn_conv_prep_f32(n, d, ptr(dY), dY.stride(0), ptr(Y), 0 if Y is None else Y.stride(0), ptr(norm), epi, p, ptr(G),
+                                          0 if G is None else G.stride(0), ptr(db), ptr(ws), nbytes, _stream()), "ctgcn_gcn_conv_prep_f32")
+    return (dY if G is None else G), db
+
+
+class _GcnConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, bias, adj, epi, p, key):
+        Y, norm = _gcn_conv_fwd(adj, S, bias, epi, p, key)
+        ctx.adj, ctx.epi, ctx.p = adj, epi, p
+        ctx.save_for_backward(*((Y,) if epi == GCN_EPI_RELU else (Y, norm) if epi == GCN_EPI_L2NORM else ()))
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        saved = ctx.saved_tensors
+        Y = saved[0] if saved else None
+        norm = saved[1] if len(saved) > 1 else None
+        need_dS, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        G, db = _gcn_conv_prep(_row_view(dY), Y, norm, ctx.epi, ctx.p, want_db=need_db)
+        dS = _gcn_conv_fwd(ctx.adj.transposed(), G, None, GCN_EPI_NONE)[0] if need_dS else None
+        return dS, db, None, None, None, None
+
+
+def gcn_conv(S, adj, bias=None, epi=GCN_EPI_NONE, p=0.0, key=0, out=None):
+    """Y = epi(Â S + bias) for any GcnAdj (symmetric or not), differentiable in S and bias.  epi: GCN_EPI_NONE; GCN_EPI_RELU, followed
+    by dropout with probability p when p > 0 (entry (i, c) kept iff the counter-based draw u01(key, i, c) >= p, kept entries scaled by
+    1 / (1 - p)); GCN_EPI_L2NORM, F.normalize(p=2) over each row.  The backward is one N x d pre-pass (the gradient before the epilogue
+    and the bias gradient) and the plain aggregation over adj.transposed().  out (inference only): a [n, d] view with unit column
+    stride that receives Y, e.g. slot t of a [n, T, d] sequence buffer."""
+    _need_cuda(S, adj.val, bias, out)
+    if epi not in (GCN_EPI_NONE, GCN_EPI_RELU, GCN_EPI_L2NORM):
+        raise ValueError("epi must be GCN_EPI_NONE, GCN_EPI_RELU or GCN_EPI_L2NORM")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p must lie in [0, 1), got %r" % p)
+    if S.dim() != 2 or S.shape[0] != adj.n:
+        raise ValueError("S must be [%d, d], got %s" % (adj.n, tuple(S.shape)))
+    if S.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        raise TypeError("fp32 features and bias expected")
+    if S.device != adj.device or (bias is not None and bias.device != S.device):
+        raise ValueError("S, bias and the adjacency must be on one device")
+    if bias is not None and tuple(bias.shape) != (S.shape[1],):
+        raise ValueError("bias must have %d entries" % S.shape[1])
+    S = _row_view(S)
+    key = int(key) & (2 ** 64 - 1)
+    if out is None:
+        return _GcnConv.apply(S, None if bias is None else bias.contiguous(), adj, int(epi), p, key)
+    if torch.is_grad_enabled() and (S.requires_grad or (bias is not None and bias.requires_grad)):
+        raise RuntimeError("gcn_conv(out=...) is an inference path")
+    if out.dtype != torch.float32 or out.device != S.device or tuple(out.shape) != tuple(S.shape) or out.stride(1) != 1 or out.stride(0) < S.shape[1]:
+        raise ValueError("out must be an fp32 [%d, %d] view with unit column stride on %s" % (S.shape[0], S.shape[1], S.device))
+    return _gcn_conv_fwd(adj, S.detach(), None if bias is None else bias.detach().contiguous(), int(epi), p, key, out=out)[0]
+

@@ -886,6 +886,34 @@ int ctgcn_gcn_layer_bwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const 
                             int64_t lddy, const float *Y, int64_t ldy, int32_t act, float *dS, int64_t ldds, const int32_t *long_rows,
                             int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * GCN step of the GCN / GCRN baselines (reference baseline/gcn.py:36-43, :84-88, baseline/gcrn.py:56-57; ctgcn_amd/baseline/gcn.py,
+ * gcrn.py), ctgcn_gcn.hip.  Same CSR, long-row and workspace rules as ctgcn_gcn_layer_fwd_f32; the matrix need not be symmetric.
+ *
+ * ctgcn_gcn_conv_fwd_f32: Y[i] = epi(Σ_e val[e] · S[col[e]] + bias); bias [d] may be null.  epi:
+ *   0  none;
+ *   1  ReLU, then dropout when p > 0: entry (i, c) is kept iff u01(key, i, c) >= p (ctgcn_rng.h's splitmix64 draw, compared in
+ *      double) and scaled by 1 / (1 - p) in fp32; zero where dropped or where the sum is <= 0.  p = 0 is bit-identical to plain ReLU;
+ *   2  the row's L2 normalisation Y[i] = x / max(‖x‖₂, 1e-12) (F.normalize), with norm[i] = ‖x‖₂ written as well (norm required).
+ *   0 <= p < 1 is checked for every epi and used by epi 1 only.
+ * ctgcn_gcn_conv_prep_f32: the backward's N x d pass.  G = d loss / d (the sum before the epilogue) from dY and the forward's Y:
+ *   1  G = Y > 0 ? dY / (1 - p) : 0 (an entry was kept and positive exactly when Y > 0: no mask, no key);
+ *   2  G = (dY − Y ⟨Y, dY⟩) / norm where norm >= 1e-12, else dY / 1e-12 (the clamped denominator is a constant);
+ *   0  G = dY: nothing is written, Y / G / norm may be null.
+ *   db [d], when not null, receives Σ_i G[i]: per-block partial sums in the workspace (ctgcn_gcn_conv_prep_workspace_bytes(n, d) bytes,
+ *   16-byte aligned; ctgcn_gcn_conv_prep_rows() rows per block), added in block order by a second launch.
+ * The input gradient is then dS = Âᵀ G: ctgcn_gcn_conv_fwd_f32 with epi 0 and no bias over the transposed CSR.
+ * No atomics; every sum has a fixed order: repeated calls on the same inputs are bit-identical.
+ */
+int ctgcn_gcn_conv_fwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val, const float *S, int64_t lds,
+                           const float *bias, float *Y, int64_t ldy, int32_t epi, double p, uint64_t key, float *norm,
+                           const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int32_t ctgcn_gcn_conv_prep_rows(void);
+size_t ctgcn_gcn_conv_prep_workspace_bytes(int64_t n, int32_t d);
+int ctgcn_gcn_conv_prep_f32(int64_t n, int32_t d, const float *dY, int64_t lddy, const float *Y, int64_t ldy, const float *norm, int32_t epi,
+                            double p, float *G, int64_t ldg, float *db, void *workspace, size_t workspace_bytes, void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
