@@ -22,6 +22,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 
 #include "ctgcn_rng.h"
 #include "ctgcn_try.h"
@@ -65,9 +66,6 @@ struct GcnArgs {
     int64_t ldmask;
     float *out;             // forward: Y; backward: dS
     int64_t ldout;
-    int32_t act;            // forward only: applied when a row is finished
-    const float *score_vec;
-    float *score_out;
     const int32_t *long_rows;
     int32_t n_long, long_thresh;
     int32_t chunks;         // ceil(d / VEC)
@@ -130,8 +128,44 @@ __device__ __forceinline__ typename vec_of<VEC>::type row_sum(const GcnArgs &a, 
     return P;
 }
 
-template <int VEC, int LPR, bool BWD>
-__global__ __launch_bounds__(256) void gcn_row_kernel(const GcnArgs a)
+// ------------------------------------------------------------------------------------------------ epilogues on a finished row
+// 0..2 are ctgcn_gcn_conv_fwd_f32's epi argument; EPI_RRELU is the layer's act 1 and is not accepted there
+constexpr int EPI_NONE = 0, EPI_RELU = 1, EPI_L2NORM = 2, EPI_RRELU = 3;
+constexpr float L2_EPS = 1e-12f;       // F.normalize's eps: the denominator is max(norm, eps)
+
+struct GcnEpi {
+    int32_t kind;
+    int32_t drop;           // RELU: p > 0
+    const float *bias;      // [d] or null: added before the kind is applied
+    const float *score_vec; // [d] or null: score_out[i] = Y[i] · score_vec
+    float *score_out;
+    float *norm;            // L2NORM: [n], the norm before the clamp
+    double p;
+    float scale;            // 1 / (1 - p)
+    uint64_t key;
+};
+
+// relu, then dropout: entry (row, c) is kept iff ctgcn_u01(key, row, c) >= p
+__device__ __forceinline__ float relu_drop(float v, const GcnEpi &e, int64_t row, int64_t c)
+{
+    if (!(v > 0.f)) return 0.f;
+    if (!e.drop) return v;
+    return ctgcn_u01(e.key, (uint64_t)row, (uint64_t)c) >= e.p ? v * e.scale : 0.f;
+}
+__device__ __forceinline__ f4 relu_drop(f4 v, const GcnEpi &e, int64_t row, int64_t c)
+{
+    return f4{relu_drop(v.x, e, row, c), relu_drop(v.y, e, row, c + 1), relu_drop(v.z, e, row, c + 2), relu_drop(v.w, e, row, c + 3)};
+}
+__device__ __forceinline__ float relu_grad(float g, float y, float scale) { return y > 0.f ? g * scale : 0.f; }
+__device__ __forceinline__ f4 relu_grad(f4 g, f4 y, float scale)
+{
+    return f4{relu_grad(g.x, y.x, scale), relu_grad(g.y, y.y, scale), relu_grad(g.z, y.z, scale), relu_grad(g.w, y.w, scale)};
+}
+
+// every row that is not long.  KIND is e.kind: a template parameter, so that a path carries no registers for the epilogues it does
+// not run.  The backward is the masked gather alone, KIND none: its instantiation compiles bias and score out too.
+template <int VEC, int LPR, bool BWD, int KIND>
+__global__ __launch_bounds__(256) void gcn_row_kernel(const GcnArgs a, const GcnEpi e)
 {
     using V = typename vec_of<VEC>::type;
     const int lig = threadIdx.x & (LPR - 1);
@@ -139,25 +173,45 @@ __global__ __launch_bounds__(256) void gcn_row_kernel(const GcnArgs a)
     if (row >= a.n) return;
     const int start = a.row_ptr[row], end = a.row_ptr[row + 1];
     if (a.n_long > 0 && end - start > a.long_thresh) return;      // long row: gcn_piece_kernel + gcn_final_kernel
-    const bool score = !BWD && a.score_vec && a.score_out;
-    float sc = 0.f;
+    const bool score = !BWD && e.score_vec;
+    constexpr bool l2 = KIND == EPI_L2NORM;
+    const bool one_pass = a.chunks <= LPR;                        // L2NORM: the row stays in registers until its norm is known
+    float sc = 0.f, ss = 0.f;
+    V P = V(0.f);
 
     for (int p0 = 0; p0 < a.chunks; p0 += LPR) {
         const int ch = p0 + lig;
         const bool live = ch < a.chunks;
         // dead lanes read chunk 0 (valid memory) and never store: keeps every load unconditional
         const int64_t foff = live ? (int64_t)ch * VEC : 0;
-        V P = row_sum<VEC, LPR, BWD>(a, start, end, lig, foff);
-        if (!BWD && a.act) P = rrelu(P);
+        P = row_sum<VEC, LPR, BWD>(a, start, end, lig, foff);
+        if (!BWD && e.bias) P += *(const V *)(e.bias + foff);
+        if (KIND == EPI_RRELU) P = rrelu(P);
+        else if (KIND == EPI_RELU) P = relu_drop(P, e, row, foff);
         if (live) {
-            *(V *)(a.out + row * a.ldout + foff) = P;
-            if (score) sc += vdot(P, *(const V *)(a.score_vec + foff));
+            if (l2) ss += vdot(P, P);
+            if (!(l2 && one_pass)) *(V *)(a.out + row * a.ldout + foff) = P;
+            if (score) sc += vdot(P, *(const V *)(e.score_vec + foff));
         }
     }
     if (score) {
 #pragma unroll
         for (int o = LPR / 2; o > 0; o >>= 1) sc += __shfl_xor(sc, o, LPR);
-        if (lig == 0) a.score_out[row] = sc;
+        if (lig == 0) e.score_out[row] = sc;
+    }
+    if (!l2) return;
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, LPR);
+    const float nrm = sqrtf(ss);
+    const float den = fmaxf(nrm, L2_EPS);
+    if (lig == 0) e.norm[row] = nrm;
+    if (one_pass) {
+        if (lig < a.chunks) *(V *)(a.out + row * a.ldout + (int64_t)lig * VEC) = P / den;
+    } else {
+        for (int ch = lig; ch < a.chunks; ch += LPR) {            // the chunks this lane wrote itself
+            V *q = (V *)(a.out + row * a.ldout + (int64_t)ch * VEC);
+            *q = *q / den;
+        }
     }
 }
 
@@ -195,118 +249,30 @@ __global__ __launch_bounds__(PIECE_THREADS) void gcn_piece_kernel(const GcnArgs 
     }
 }
 
-// one wave per long row: the pieces in piece order, the activation, the row and its score
-template <bool BWD>
-__global__ __launch_bounds__(64) void gcn_final_kernel(const GcnArgs a)
+// one wave per long row: the pieces in piece order, the bias, the epilogue, the row and its score
+__global__ __launch_bounds__(64) void gcn_final_kernel(const GcnArgs a, const GcnEpi e)
 {
     const int64_t row = a.long_rows[blockIdx.x];
     const int len = a.row_ptr[row + 1] - a.row_ptr[row];
     const int np = pieces_of(len, a.long_thresh, a.max_pieces);
     const float *src = a.part + (int64_t)blockIdx.x * a.max_pieces * a.part_ld;
-    const bool score = !BWD && a.score_vec && a.score_out;
-    float sc = 0.f;
-    for (int c = threadIdx.x; c < a.d; c += 64) {
-        float t = src[c];
-        for (int p = 1; p < np; ++p) t += src[(int64_t)p * a.part_ld + c];
-        if (!BWD && a.act) t = rrelu1(t);
-        a.out[row * a.ldout + c] = t;
-        if (score) sc = fmaf(t, a.score_vec[c], sc);
-    }
-    if (score) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sc += __shfl_xor(sc, o, 64);
-        if (threadIdx.x == 0) a.score_out[row] = sc;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ GCN / GCRN step: epilogues
-constexpr int EPI_NONE = 0, EPI_RELU = 1, EPI_L2NORM = 2;
-constexpr float L2_EPS = 1e-12f;       // F.normalize's eps: the denominator is max(norm, eps)
-
-struct ConvEpi {
-    const float *bias;      // [d] or null
-    float *norm;            // L2NORM: [n], the norm before the clamp
-    int32_t epi;
-    int32_t drop;           // RELU: p > 0
-    double p;
-    float scale;            // 1 / (1 - p)
-    uint64_t key;
-};
-
-// relu, then dropout: entry (row, c) is kept iff ctgcn_u01(key, row, c) >= p
-__device__ __forceinline__ float relu_drop(float v, const ConvEpi &e, int64_t row, int64_t c)
-{
-    if (!(v > 0.f)) return 0.f;
-    if (!e.drop) return v;
-    return ctgcn_u01(e.key, (uint64_t)row, (uint64_t)c) >= e.p ? v * e.scale : 0.f;
-}
-__device__ __forceinline__ f4 relu_drop(f4 v, const ConvEpi &e, int64_t row, int64_t c)
-{
-    return f4{relu_drop(v.x, e, row, c), relu_drop(v.y, e, row, c + 1), relu_drop(v.z, e, row, c + 2), relu_drop(v.w, e, row, c + 3)};
-}
-__device__ __forceinline__ float relu_grad(float g, float y, float scale) { return y > 0.f ? g * scale : 0.f; }
-__device__ __forceinline__ f4 relu_grad(f4 g, f4 y, float scale)
-{
-    return f4{relu_grad(g.x, y.x, scale), relu_grad(g.y, y.y, scale), relu_grad(g.z, y.z, scale), relu_grad(g.w, y.w, scale)};
-}
-
-template <int VEC, int LPR>
-__global__ __launch_bounds__(256) void gcn_conv_row_kernel(const GcnArgs a, const ConvEpi e)
-{
-    using V = typename vec_of<VEC>::type;
-    const int lig = threadIdx.x & (LPR - 1);
-    const int64_t row = (int64_t)blockIdx.x * (256 / LPR) + (threadIdx.x / LPR);
-    if (row >= a.n) return;
-    const int start = a.row_ptr[row], end = a.row_ptr[row + 1];
-    if (a.n_long > 0 && end - start > a.long_thresh) return;      // long row: gcn_piece_kernel + gcn_conv_final_kernel
-    const bool l2 = e.epi == EPI_L2NORM;
-    const bool one_pass = a.chunks <= LPR;                        // L2NORM: the row stays in registers until its norm is known
-    float ss = 0.f;
-    V P = V(0.f);
-
-    for (int p0 = 0; p0 < a.chunks; p0 += LPR) {
-        const int ch = p0 + lig;
-        const bool live = ch < a.chunks;
-        const int64_t foff = live ? (int64_t)ch * VEC : 0;
-        P = row_sum<VEC, LPR, false>(a, start, end, lig, foff);
-        if (e.bias) P += *(const V *)(e.bias + foff);
-        if (e.epi == EPI_RELU) P = relu_drop(P, e, row, foff);
-        if (l2 && live) ss += vdot(P, P);
-        if (live && !(l2 && one_pass)) *(V *)(a.out + row * a.ldout + foff) = P;
-    }
-    if (!l2) return;
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, LPR);
-    const float nrm = sqrtf(ss);
-    const float den = fmaxf(nrm, L2_EPS);
-    if (lig == 0) e.norm[row] = nrm;
-    if (one_pass) {
-        if (lig < a.chunks) *(V *)(a.out + row * a.ldout + (int64_t)lig * VEC) = P / den;
-    } else {
-        for (int ch = lig; ch < a.chunks; ch += LPR) {            // the chunks this lane wrote itself
-            V *q = (V *)(a.out + row * a.ldout + (int64_t)ch * VEC);
-            *q = *q / den;
-        }
-    }
-}
-
-// one wave per long row: the pieces in piece order, the bias, the epilogue
-__global__ __launch_bounds__(64) void gcn_conv_final_kernel(const GcnArgs a, const ConvEpi e)
-{
-    const int64_t row = a.long_rows[blockIdx.x];
-    const int len = a.row_ptr[row + 1] - a.row_ptr[row];
-    const int np = pieces_of(len, a.long_thresh, a.max_pieces);
-    const float *src = a.part + (int64_t)blockIdx.x * a.max_pieces * a.part_ld;
-    float ss = 0.f;
+    float sc = 0.f, ss = 0.f;
     for (int c = threadIdx.x; c < a.d; c += 64) {
         float t = src[c];
         for (int p = 1; p < np; ++p) t += src[(int64_t)p * a.part_ld + c];
         if (e.bias) t += e.bias[c];
-        if (e.epi == EPI_RELU) t = relu_drop(t, e, row, c);
+        if (e.kind == EPI_RRELU) t = rrelu1(t);
+        else if (e.kind == EPI_RELU) t = relu_drop(t, e, row, c);
         ss = fmaf(t, t, ss);
         a.out[row * a.ldout + c] = t;
+        if (e.score_vec) sc = fmaf(t, e.score_vec[c], sc);
     }
-    if (e.epi != EPI_L2NORM) return;
+    if (e.score_vec) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sc += __shfl_xor(sc, o, 64);
+        if (threadIdx.x == 0) e.score_out[row] = sc;
+    }
+    if (e.kind != EPI_L2NORM) return;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
     const float nrm = sqrtf(ss);
@@ -418,33 +384,58 @@ int fail(int code, const char *what, const char *text)
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <int VEC, int LPR, bool BWD>
-void launch_rows(const GcnArgs &a, hipStream_t st)
+// p as [.][ld] rows, or a vector with ld 0; a null p is an operand the call does not have
+struct Operand {
+    const void *p;
+    int64_t ld;
+};
+
+// float4 rows: d and every leading dimension a multiple of 4, every base 16-byte aligned
+bool float4_rows(int32_t d, std::initializer_list<Operand> operands)
 {
-    const int64_t rows_per_block = 256 / LPR;
-    hipLaunchKernelGGL((gcn_row_kernel<VEC, LPR, BWD>), dim3((unsigned)((a.n + rows_per_block - 1) / rows_per_block)), dim3(256), 0, st, a);
+    if (d % 4) return false;
+    for (const Operand &o : operands)
+        if (o.p && (o.ld % 4 || !aligned16(o.p))) return false;
+    return true;
 }
 
-template <int VEC, bool BWD>
-int launch(GcnArgs a, hipStream_t st)
+template <int VEC, bool BWD, int KIND>
+int launch(GcnArgs a, const GcnEpi &e, hipStream_t st)
 {
     a.chunks = (a.d + VEC - 1) / VEC;
-    if (a.chunks <= 4) launch_rows<VEC, 4, BWD>(a, st);
-    else if (a.chunks <= 8) launch_rows<VEC, 8, BWD>(a, st);
-    else if (a.chunks <= 16) launch_rows<VEC, 16, BWD>(a, st);
-    else if (a.chunks <= 32) launch_rows<VEC, 32, BWD>(a, st);
-    else launch_rows<VEC, 64, BWD>(a, st);
+    const int lpr = a.chunks <= 4 ? 4 : a.chunks <= 8 ? 8 : a.chunks <= 16 ? 16 : a.chunks <= 32 ? 32 : 64;
+    const dim3 grid((unsigned)((a.n + 256 / lpr - 1) / (256 / lpr)));
+    switch (lpr) {
+    case 4: hipLaunchKernelGGL((gcn_row_kernel<VEC, 4, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
+    case 8: hipLaunchKernelGGL((gcn_row_kernel<VEC, 8, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
+    case 16: hipLaunchKernelGGL((gcn_row_kernel<VEC, 16, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
+    case 32: hipLaunchKernelGGL((gcn_row_kernel<VEC, 32, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
+    default: hipLaunchKernelGGL((gcn_row_kernel<VEC, 64, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
+    }
     CTGCN_TRY(hipGetLastError());
     if (a.n_long > 0) {
         hipLaunchKernelGGL((gcn_piece_kernel<VEC, BWD>), dim3((unsigned)a.max_pieces, (unsigned)a.n_long), dim3(PIECE_THREADS), 0, st, a);
         CTGCN_TRY(hipGetLastError());
-        hipLaunchKernelGGL((gcn_final_kernel<BWD>), dim3((unsigned)a.n_long), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(gcn_final_kernel, dim3((unsigned)a.n_long), dim3(64), 0, st, a, e);
         CTGCN_TRY(hipGetLastError());
     }
     return CTGCN_OK;
 }
 
-// checks shared by the two layer entry points; fills the long-row fields
+// picks the launcher's instantiation for a call: float4 or scalar rows, the backward's masked gather or the forward with e.kind
+int dispatch(const GcnArgs &a, const GcnEpi &e, bool bwd, bool v4, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (bwd) return v4 ? launch<4, true, EPI_NONE>(a, e, st) : launch<1, true, EPI_NONE>(a, e, st);
+    switch (e.kind) {
+    case EPI_RELU: return v4 ? launch<4, false, EPI_RELU>(a, e, st) : launch<1, false, EPI_RELU>(a, e, st);
+    case EPI_L2NORM: return v4 ? launch<4, false, EPI_L2NORM>(a, e, st) : launch<1, false, EPI_L2NORM>(a, e, st);
+    case EPI_RRELU: return v4 ? launch<4, false, EPI_RRELU>(a, e, st) : launch<1, false, EPI_RRELU>(a, e, st);
+    default: return v4 ? launch<4, false, EPI_NONE>(a, e, st) : launch<1, false, EPI_NONE>(a, e, st);
+    }
+}
+
+// checks shared by the three gather entry points; fills the long-row fields
 int set_common(GcnArgs &a, const char *what, int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val,
                const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes)
 {
@@ -465,29 +456,6 @@ int set_common(GcnArgs &a, const char *what, int64_t n, int32_t d, const int32_t
         const size_t mp = workspace_bytes / one;
         a.max_pieces = (int32_t)(mp > 4096 ? 4096 : mp);
         a.part = (float *)workspace;
-    }
-    return CTGCN_OK;
-}
-
-template <int VEC>
-int launch_conv(GcnArgs a, const ConvEpi &e, hipStream_t st)
-{
-    a.chunks = (a.d + VEC - 1) / VEC;
-    const int lpr = a.chunks <= 4 ? 4 : a.chunks <= 8 ? 8 : a.chunks <= 16 ? 16 : a.chunks <= 32 ? 32 : 64;
-    const dim3 grid((unsigned)((a.n + 256 / lpr - 1) / (256 / lpr)));
-    switch (lpr) {
-    case 4: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 4>), grid, dim3(256), 0, st, a, e); break;
-    case 8: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 8>), grid, dim3(256), 0, st, a, e); break;
-    case 16: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 16>), grid, dim3(256), 0, st, a, e); break;
-    case 32: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 32>), grid, dim3(256), 0, st, a, e); break;
-    default: hipLaunchKernelGGL((gcn_conv_row_kernel<VEC, 64>), grid, dim3(256), 0, st, a, e); break;
-    }
-    CTGCN_TRY(hipGetLastError());
-    if (a.n_long > 0) {
-        hipLaunchKernelGGL((gcn_piece_kernel<VEC, false>), dim3((unsigned)a.max_pieces, (unsigned)a.n_long), dim3(PIECE_THREADS), 0, st, a);
-        CTGCN_TRY(hipGetLastError());
-        hipLaunchKernelGGL(gcn_conv_final_kernel, dim3((unsigned)a.n_long), dim3(64), 0, st, a, e);
-        CTGCN_TRY(hipGetLastError());
     }
     return CTGCN_OK;
 }
@@ -565,9 +533,10 @@ extern "C" int ctgcn_gcn_layer_fwd_f32(int64_t n, int32_t d, const int32_t *row_
     if (int rc = set_common(a, what, n, d, row_ptr, col, val, long_rows, n_long, long_threshold, workspace, workspace_bytes)) return rc;
     if (n == 0) return CTGCN_OK;
     if (!S || !Y) return fail(CTGCN_E_INVALID, what, "null pointer");
-    a.src = S; a.ldsrc = lds; a.out = Y; a.ldout = ldy; a.act = act; a.score_vec = score_vec; a.score_out = score_out;
-    const bool v4 = d % 4 == 0 && lds % 4 == 0 && ldy % 4 == 0 && aligned16(S) && aligned16(Y) && (!score_vec || aligned16(score_vec));
-    return v4 ? launch<4, false>(a, (hipStream_t)stream) : launch<1, false>(a, (hipStream_t)stream);
+    a.src = S; a.ldsrc = lds; a.out = Y; a.ldout = ldy;
+    GcnEpi e{};
+    e.kind = act ? EPI_RRELU : EPI_NONE; e.score_vec = score_vec; e.score_out = score_out;
+    return dispatch(a, e, false, float4_rows(d, {{S, lds}, {Y, ldy}, {score_vec, 0}}), stream);
 }
 
 extern "C" int ctgcn_gcn_layer_bwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val, const float *dY,
@@ -582,9 +551,8 @@ extern "C" int ctgcn_gcn_layer_bwd_f32(int64_t n, int32_t d, const int32_t *row_
     if (int rc = set_common(a, what, n, d, row_ptr, col, val, long_rows, n_long, long_threshold, workspace, workspace_bytes)) return rc;
     if (n == 0) return CTGCN_OK;
     if (!dY || !dS || (act && !Y)) return fail(CTGCN_E_INVALID, what, "null pointer");
-    a.src = dY; a.ldsrc = lddy; a.ymask = act ? Y : nullptr; a.ldmask = act ? ldy : 0; a.out = dS; a.ldout = ldds; a.act = act;
-    const bool v4 = d % 4 == 0 && lddy % 4 == 0 && ldds % 4 == 0 && aligned16(dY) && aligned16(dS) && (!act || (ldy % 4 == 0 && aligned16(Y)));
-    return v4 ? launch<4, true>(a, (hipStream_t)stream) : launch<1, true>(a, (hipStream_t)stream);
+    a.src = dY; a.ldsrc = lddy; a.ymask = act ? Y : nullptr; a.ldmask = act ? ldy : 0; a.out = dS; a.ldout = ldds;
+    return dispatch(a, GcnEpi{}, true, float4_rows(d, {{dY, lddy}, {dS, ldds}, {a.ymask, ldy}}), stream);
 }
 
 extern "C" int ctgcn_gcn_conv_fwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val, const float *S,
@@ -601,10 +569,9 @@ extern "C" int ctgcn_gcn_conv_fwd_f32(int64_t n, int32_t d, const int32_t *row_p
     if (n == 0) return CTGCN_OK;
     if (!S || !Y || (epi == EPI_L2NORM && !norm)) return fail(CTGCN_E_INVALID, what, "null pointer");
     a.src = S; a.ldsrc = lds; a.out = Y; a.ldout = ldy;
-    ConvEpi e{};
-    e.bias = bias; e.norm = norm; e.epi = epi; e.drop = epi == EPI_RELU && p > 0.0; e.p = p; e.scale = 1.0f / (1.0f - (float)p); e.key = key;
-    const bool v4 = d % 4 == 0 && lds % 4 == 0 && ldy % 4 == 0 && aligned16(S) && aligned16(Y) && (!bias || aligned16(bias));
-    return v4 ? launch_conv<4>(a, e, (hipStream_t)stream) : launch_conv<1>(a, e, (hipStream_t)stream);
+    GcnEpi e{};
+    e.kind = epi; e.bias = bias; e.norm = norm; e.drop = epi == EPI_RELU && p > 0.0; e.p = p; e.scale = 1.0f / (1.0f - (float)p); e.key = key;
+    return dispatch(a, e, false, float4_rows(d, {{S, lds}, {Y, ldy}, {bias, 0}}), stream);
 }
 
 extern "C" int32_t ctgcn_gcn_conv_prep_rows(void) { return PREP_ROWS; }
@@ -636,7 +603,7 @@ extern "C" int ctgcn_gcn_conv_prep_f32(int64_t n, int32_t d, const float *dY, in
     a.G = wants_g ? G : nullptr; a.ldg = ldg; a.part = db ? (float *)workspace : nullptr; a.part_ld = (d + 3) & ~3;
     hipStream_t st = (hipStream_t)stream;
     const int64_t blocks = (n + PREP_ROWS - 1) / PREP_ROWS;
-    const bool v4 = d % 4 == 0 && lddy % 4 == 0 && aligned16(dY) && (!wants_g || (ldy % 4 == 0 && ldg % 4 == 0 && aligned16(Y) && aligned16(G)));
+    const bool v4 = float4_rows(d, {{dY, lddy}, {a.Y, ldy}, {a.G, ldg}});
     a.chunks = v4 ? d / 4 : d;
     if (v4) hipLaunchKernelGGL(gcn_conv_prep_kernel<4>, dim3((unsigned)blocks), dim3(64 * PREP_WAVES), 0, st, a);
     else hipLaunchKernelGGL(gcn_conv_prep_kernel<1>, dim3((unsigned)blocks), dim3(64 * PREP_WAVES), 0, st, a);

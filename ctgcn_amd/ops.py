@@ -2098,8 +2098,7 @@ class _GcnLayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dY, *_):
         Y = ctx.saved_tensors[0] if ctx.act else None
-        dY = dY if (dY.stride(1) == 1 and dY.stride(0) >= dY.shape[1]) else dY.contiguous()
-        return _gcn_bwd(ctx.adj, dY, Y, ctx.act), None, None, None
+        return _gcn_bwd(ctx.adj, _row_view(dY), Y, ctx.act), None, None, None
 
 
 def gcn_layer(S, adj, act=GCN_ACT_RRELU, score_vec=None):
@@ -2114,7 +2113,7 @@ def gcn_layer(S, adj, act=GCN_ACT_RRELU, score_vec=None):
         raise TypeError("fp32 features expected")
     if S.device != adj.device:
         raise ValueError("S on %s but adjacency on %s" % (S.device, adj.device))
-    S = S if (S.stride(1) == 1 and S.stride(0) >= S.shape[1]) else S.contiguous()
+    S = _row_view(S)
     if score_vec is not None:
         score_vec = score_vec.detach().reshape(-1).to(torch.float32).contiguous()
         if score_vec.numel() != S.shape[1]:
