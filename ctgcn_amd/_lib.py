@@ -162,6 +162,16 @@ SIGNATURES = {
     "ctgcn_gcn_conv_prep_rows": (_i32, []),
     "ctgcn_gcn_conv_prep_workspace_bytes": (_sz, [_i64, _i32]),
     "ctgcn_gcn_conv_prep_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _c.c_double, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ctgcn_gat_piece_floats": (_i32, [_i32, _i32]),
+    "ctgcn_gat_da_workspace_bytes": (_sz, [_i64, _i32]),
+    "ctgcn_gat_da_f32": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_gat_fwd_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _c.c_double, _i32, _c.c_double, _c.c_uint64, _c.c_double,
+                                 _c.c_uint64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_gat_bwd_prep_f32": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _c.c_double, _c.c_uint64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "ctgcn_gat_bwd_row_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _c.c_double, _c.c_double, _c.c_uint64, _vp, _i64,
+                                     _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_gat_bwd_col_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _c.c_double, _c.c_double, _c.c_uint64,
+                                     _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

@@ -1,4 +1,5 @@
 """Methods CTGCN is compared against (the reference's `baseline` package), on the same HIP library."""
 from .egcn import EvolveGCN  # noqa: F401
+from .gat import GAT, SpGraphAttentionLayer  # noqa: F401
 from .gcn import GCN, GraphConvolution  # noqa: F401
 from .gcrn import GCRN  # noqa: F401

@@ -24,7 +24,7 @@ from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLo
                       epoch_batch_seed)
 
 _S_MODELS = ('CGCN-S', 'CTGCN-S')
-_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN')      # the baselines: single-output, trained like the -C models
+_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT')      # the baselines: single-output, trained like the -C models
 
 
 def batch_count(node_num, batch_size):

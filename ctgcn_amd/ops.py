@@ -2206,3 +2206,146 @@ def gcn_conv(S, adj, bias=None, epi=GCN_EPI_NONE, p=0.0, key=0, out=None):
         raise ValueError("out must be an fp32 [%d, %d] view with unit column stride on %s" % (S.shape[0], S.shape[1], S.device))
     return _gcn_conv_fwd(adj, S.detach(), None if bias is None else bias.detach().contiguous(), int(epi), p, key, out=out)[0]
 
+
+
+# ------------------------------------------------------------------------- graph-attention step of the GAT baseline (ctgcn_gat.hip)
+GAT_EPI_NONE, GAT_EPI_ELU, GAT_EPI_ELU_DROPOUT = 0, 1, 2
+
+
+def _gat_long(adj, d, heads):
+    """the long-row arguments of a gather: the pieces hold two [d] sums and a [heads] one"""
+    ws, nbytes = adj.workspace(int(_lib.load().ctgcn_gat_piece_floats(d, heads)))
+    return ptr(adj.long_rows), 0 if adj.long_rows is None else adj.long_rows.numel(), adj.long_threshold, ptr(ws), nbytes
+
+
+def _gat_fwd(adj, S, a_src, a_dst, heads, alpha, epi, p_att=0.0, key=0, p_feat=0.0, fkey=0):
+    """(out, Y, u, v, m, Z): ctgcn_gat_fwd_f32.  Y is the sum before the epilogue: out itself for GAT_EPI_NONE."""
+    lib = _lib.load()
+    n, d = S.shape
+    dev = S.device
+    out = torch.empty(n, d, dtype=torch.float32, device=dev)
+    Y = torch.empty(n, d, dtype=torch.float32, device=dev) if epi != GAT_EPI_NONE else None
+    u, v, m, Z = (torch.empty(n, heads, dtype=torch.float32, device=dev) for _ in range(4))
+    with torch.cuda.device(dev), _timed("gat_fwd", n=n, d=d, heads=heads, nnz=adj.nnz):
+        check(lib.ctgcn_gat_fwd_f32(n, d, heads, ptr(adj.row_ptr), ptr(adj.col), ptr(S), S.stride(0), ptr(a_src), ptr(a_dst), alpha, epi, p_att,
+                                    key, p_feat, fkey, ptr(out), out.stride(0), ptr(Y), 0 if Y is None else Y.stride(0), ptr(u), ptr(v), ptr(m),
+                                    ptr(Z), *_gat_long(adj, d, heads), _stream()), "ctgcn_gat_fwd_f32")
+    return out, (out if Y is None else Y), u, v, m, Z
+
+
+def _gat_bwd_prep(dY, Y, u, m, Z, heads, epi, p_feat=0.0, fkey=0):
+    """(G, pack): ctgcn_gat_bwd_prep_f32.  G is dY itself for GAT_EPI_NONE; pack [n, heads, 4] = {u, m, 1 / Z, D}."""
+    lib = _lib.load()
+    n, d = dY.shape
+    dev = dY.device
+    G = torch.empty(n, d, dtype=torch.float32, device=dev) if epi != GAT_EPI_NONE else None
+    pack = torch.empty(n, heads, 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed("gat_bwd_prep", n=n, d=d, heads=heads):
+        check(lib.ctgcn_gat_bwd_prep_f32(n, d, heads, ptr(dY), dY.stride(0), ptr(Y), Y.stride(0), epi, p_feat, fkey, ptr(u), ptr(m), ptr(Z),
+                                         ptr(G), 0 if G is None else G.stride(0), ptr(pack), _stream()), "ctgcn_gat_bwd_prep_f32")
+    return (dY if G is None else G), pack
+
+
+def _gat_bwd_row(adj, S, G, v, pack, heads, alpha, p_att=0.0, key=0):
+    """du [n, heads]: ctgcn_gat_bwd_row_f32 over the CSR"""
+    lib = _lib.load()
+    n, d = S.shape
+    dev = S.device
+    R = torch.empty(n, d, dtype=torch.float32, device=dev)
+    csum, du = (torch.empty(n, heads, dtype=torch.float32, device=dev) for _ in range(2))
+    with torch.cuda.device(dev), _timed("gat_bwd_row", n=n, d=d, heads=heads, nnz=adj.nnz):
+        check(lib.ctgcn_gat_bwd_row_f32(n, d, heads, ptr(adj.row_ptr), ptr(adj.col), ptr(S), S.stride(0), ptr(G), G.stride(0), ptr(v), ptr(pack),
+                                        alpha, p_att, key, ptr(R), R.stride(0), ptr(csum), ptr(du), *_gat_long(adj, d, heads), _stream()),
+              "ctgcn_gat_bwd_row_f32")
+    return du
+
+
+def _gat_bwd_col(adj_t, S, G, v, pack, a_src, a_dst, heads, alpha, p_att=0.0, key=0, du=None):
+    """(dS or None, dv [n, heads]): ctgcn_gat_bwd_col_f32 over the transposed CSR; dS only with du"""
+    lib = _lib.load()
+    n, d = S.shape
+    dev = S.device
+    dS = torch.empty(n, d, dtype=torch.float32, device=dev) if du is not None else None
+    B = torch.empty(n, d, dtype=torch.float32, device=dev)
+    ksum, dv = (torch.empty(n, heads, dtype=torch.float32, device=dev) for _ in range(2))
+    with torch.cuda.device(dev), _timed("gat_bwd_col", n=n, d=d, heads=heads, nnz=adj_t.nnz):
+        check(lib.ctgcn_gat_bwd_col_f32(n, d, heads, ptr(adj_t.row_ptr), ptr(adj_t.col), ptr(G), G.stride(0), ptr(S), S.stride(0), ptr(v), ptr(pack),
+                                        ptr(a_src), ptr(a_dst), alpha, p_att, key, ptr(du), ptr(dS), 0 if dS is None else dS.stride(0), ptr(B),
+                                        B.stride(0), ptr(ksum), ptr(dv), *_gat_long(adj_t, d, heads), _stream()), "ctgcn_gat_bwd_col_f32")
+    return dS, dv
+
+
+def _gat_da(S, du, dv, heads):
+    """(da_src, da_dst), each [heads, F] or None: ctgcn_gat_da_f32, sum_i du[i, h] S_i^h and sum_i dv[i, h] S_i^h from one read of S"""
+    lib = _lib.load()
+    n, d = S.shape
+    dev = S.device
+    da_src = torch.empty(heads, d // heads, dtype=torch.float32, device=dev) if du is not None else None
+    da_dst = torch.empty(heads, d // heads, dtype=torch.float32, device=dev) if dv is not None else None
+    nbytes = int(lib.ctgcn_gat_da_workspace_bytes(n, d))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _timed("gat_da", n=n, d=d, heads=heads):
+        check(lib.ctgcn_gat_da_f32(n, d, heads, ptr(S), S.stride(0), ptr(du), ptr(dv), ptr(da_src), ptr(da_dst), ptr(ws), nbytes, _stream()),
+              "ctgcn_gat_da_f32")
+    return da_src, da_dst
+
+
+class _GatConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, a_src, a_dst, adj, heads, alpha, epi, p_att, key, p_feat, fkey):
+        out, Y, u, v, m, Z = _gat_fwd(adj, S, a_src, a_dst, heads, alpha, epi, p_att, key, p_feat, fkey)
+        ctx.adj, ctx.cfg = adj, (heads, alpha, epi, p_att, key, p_feat, fkey)
+        ctx.save_for_backward(S, a_src, a_dst, Y, u, v, m, Z)
+        return out
+
+    @staticmethod
+    def backward(ctx, dY):
+        S, a_src, a_dst, Y, u, v, m, Z = ctx.saved_tensors
+        heads, alpha, epi, p_att, key, p_feat, fkey = ctx.cfg
+        need_dS, need_src, need_dst = ctx.needs_input_grad[:3]
+        dS = da_src = da_dst = None
+        if need_dS or need_src or need_dst:
+            G, pack = _gat_bwd_prep(_row_view(dY), Y, u, m, Z, heads, epi, p_feat, fkey)
+            du = _gat_bwd_row(ctx.adj, S, G, v, pack, heads, alpha, p_att, key) if (need_dS or need_src) else None
+            if need_dS or need_dst:
+                dS, dv = _gat_bwd_col(ctx.adj.transposed(), S, G, v, pack, a_src, a_dst, heads, alpha, p_att, key, du if need_dS else None)
+            if need_src or need_dst:
+                da_src, da_dst = _gat_da(S, du if need_src else None, dv if need_dst else None, heads)
+        return (dS, da_src, da_dst) + (None,) * 8
+
+
+def gat_conv(S, a_src, a_dst, adj, heads, alpha=0.2, epi=GAT_EPI_NONE, p_att=0.0, key=0, p_feat=0.0, fkey=0):
+    """One graph-attention layer of `heads` heads over the pattern of any GcnAdj (its values are not read; stored entries count even
+    when their value is 0), differentiable in S, a_src and a_dst.  S [n, d] holds x W_h in columns [hF, (h+1)F), F = d / heads;
+    a_src / a_dst [heads, F] are the two halves of the reference's a [1, 2F] per head.  For a stored entry (i, j) and head h:
+        l_ij = -leakyrelu_alpha(a_src_h · S_i^h + a_dst_h · S_j^h),  e_ij = exp(l_ij - max_j l_ij),  Z_i = sum_j e_ij,
+        Y_i^h = (sum_j q_ij e_ij S_j^h) / Z_i,  q_ij = [u01(key + h, i, j) >= p_att] / (1 - p_att)  (1 at p_att = 0: no draw is made)
+    and the result is epi(Y): GAT_EPI_NONE; GAT_EPI_ELU; GAT_EPI_ELU_DROPOUT, ELU followed by dropout of entry (i, c) iff
+    u01(fkey, i, c) < p_feat, kept entries scaled by 1 / (1 - p_feat).  The shift by the row maximum is the only departure from the
+    reference's arithmetic (it exponentiates the unshifted logits and fails its NaN assertion once they leave fp32 exp's range).
+    A row without stored entries gives an output row of exact zeros and no gradient; the reference would fail its NaN assertion there
+    (0 / 0), and its loader's add_eye makes such rows impossible.  The backward runs over adj and adj.transposed() and computes only
+    the gradients that are asked for; no mask and nothing of nnz x F elements is stored."""
+    _need_cuda(S, a_src, a_dst, adj.val)
+    heads = int(heads)
+    if epi not in (GAT_EPI_NONE, GAT_EPI_ELU, GAT_EPI_ELU_DROPOUT):
+        raise ValueError("epi must be GAT_EPI_NONE, GAT_EPI_ELU or GAT_EPI_ELU_DROPOUT")
+    p_att, p_feat, alpha = float(p_att), float(p_feat), float(alpha)
+    if not (0.0 <= p_att < 1.0 and 0.0 <= p_feat < 1.0):
+        raise ValueError("dropout p must lie in [0, 1), got %r and %r" % (p_att, p_feat))
+    if alpha != alpha or alpha in (float("inf"), float("-inf")):
+        raise ValueError("alpha must be finite")
+    if S.dim() != 2 or S.shape[0] != adj.n:
+        raise ValueError("S must be [%d, d], got %s" % (adj.n, tuple(S.shape)))
+    if heads < 1 or S.shape[1] < 1 or S.shape[1] % heads:
+        raise ValueError("d = %d is not a positive multiple of heads = %d" % (S.shape[1], heads))
+    want = (heads, S.shape[1] // heads)
+    if tuple(a_src.shape) != want or tuple(a_dst.shape) != want:
+        raise ValueError("a_src and a_dst must be [%d, %d]" % want)
+    if S.dtype != torch.float32 or a_src.dtype != torch.float32 or a_dst.dtype != torch.float32:
+        raise TypeError("fp32 features and attention vectors expected")
+    if S.device != adj.device or a_src.device != S.device or a_dst.device != S.device:
+        raise ValueError("S, a_src, a_dst and the adjacency must be on one device")
+    mask = 2 ** 64 - 1
+    return _GatConv.apply(_row_view(S), a_src.contiguous(), a_dst.contiguous(), adj, heads, alpha, int(epi), p_att, int(key) & mask, p_feat,
+                          int(fkey) & mask)

@@ -914,6 +914,53 @@ size_t ctgcn_gcn_conv_prep_workspace_bytes(int64_t n, int32_t d);
 int ctgcn_gcn_conv_prep_f32(int64_t n, int32_t d, const float *dY, int64_t lddy, const float *Y, int64_t ldy, const float *norm, int32_t epi,
                             double p, float *G, int64_t ldg, float *db, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Graph-attention step of the GAT baseline (reference baseline/gat.py:65-105; ctgcn_amd/baseline/gat.py), ctgcn_gat.hip.
+ * One layer: `heads` heads of width F = d / heads over S [n, d] (columns [hF, (h+1)F) hold x W_h), a_src / a_dst [heads, F], and the
+ * pattern of a CSR (row_ptr / col and the long-row list as in ctgcn_gcn_layer_fwd_f32; the values are not read).  For entry (i, j):
+ *   z = u_i + v_j, l = -leakyrelu_alpha(z), m_i = max_j l, e = exp(l - m_i), Z_i = Σ_j e, q = keep(key + h, i, j) / (1 - p_att),
+ *   Y_i^h = (Σ_j q e S_j^h) / Z_i;  keep(k, i, j) = u01(k, i, j) >= p_att (ctgcn_rng.h, compared in double); p_att = 0 draws nothing.
+ *   A row without entries gives exact zeros (and m = Z = 0).
+ * ctgcn_gat_fwd_f32: u, v, m, Z [n, heads] and out = epi(Y) are written.  epi: 0 none; 1 ELU; 2 ELU, then feature dropout when
+ *   p_feat > 0: entry (i, c) kept iff u01(fkey, i, c) >= p_feat, scaled by 1 / (1 - p_feat).  With epi != 0, Y [n, d] receives the sums
+ *   before the epilogue, which the backward reads (Y may be null with epi 0: out is Y).
+ * ctgcn_gat_bwd_prep_f32: G = d loss / d Y from dY through the epilogue (mask regenerated from fkey; with epi 0 nothing is written
+ *   and G = dY), D_i = G_i^h · Y_i^h, and pack [n, heads, 4] = {u, m, 1 / Z (0 where Z = 0), D}, 16-byte aligned.
+ * ctgcn_gat_bwd_row_f32: over the CSR.  R_i^h = Σ_j s q p S_j^h (p = e / Z_i, s = z > 0 ? 1 : alpha), csum_i = Σ_j s p, then
+ *   du_i = D_i csum_i − G_i^h · R_i^h.  R [n, d] and csum [n, heads] are scratch of the call.
+ * ctgcn_gat_bwd_col_f32: over the transposed CSR (row_ptr / col / long rows of Aᵀ).  A_j^h = Σ_i q p G_i^h into dS, B_j^h = Σ_i s q p G_i^h,
+ *   ksum_j = Σ_i s p D_i, then dv_j = ksum_j − S_j^h · B_j^h and dS_j^h = A_j^h + du_j a_src_h + dv_j a_dst_h.  B [n, d] and ksum
+ *   [n, heads] are scratch.  du and dS may both be null: dv alone.
+ * ctgcn_gat_da_f32: da_src [heads, F] = Σ_i du_i S_i^h and da_dst = Σ_i dv_i S_i^h from one read of S: per-block column sums in the
+ *   workspace (ctgcn_gat_da_workspace_bytes(n, d) bytes), added in block order by a second launch.  du / da_src or dv / da_dst may
+ *   be null together; n = 0 writes zeros.
+ * Long rows: workspace of n_long · pieces · ctgcn_gat_piece_floats(d, heads) · 4 bytes, 16-byte aligned (at least one piece per row).
+ * Returns CTGCN_E_INVALID for null pointers, n < 0 or n >= 2^31, d < 1, heads < 1, d % heads != 0, a leading dimension below d, a p
+ * outside [0, 1) or a non-finite alpha; CTGCN_E_WORKSPACE for a workspace that is too small; 0 for n = 0.
+ * No atomics; every sum has a fixed order: repeated calls on the same inputs are bit-identical.
+ */
+int32_t ctgcn_gat_piece_floats(int32_t d, int32_t heads);
+size_t ctgcn_gat_da_workspace_bytes(int64_t n, int32_t d);
+int ctgcn_gat_da_f32(int64_t n, int32_t d, int32_t heads, const float *S, int64_t lds, const float *du, const float *dv, float *da_src,
+                     float *da_dst, void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_gat_fwd_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S, int64_t lds,
+                      const float *a_src, const float *a_dst, double alpha, int32_t epi, double p_att, uint64_t key, double p_feat,
+                      uint64_t fkey, float *out, int64_t ldout, float *Y, int64_t ldy, float *u, float *v, float *m, float *Z,
+                      const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
+                      void *stream);
+int ctgcn_gat_bwd_prep_f32(int64_t n, int32_t d, int32_t heads, const float *dY, int64_t lddy, const float *Y, int64_t ldy, int32_t epi,
+                           double p_feat, uint64_t fkey, const float *u, const float *m, const float *Z, float *G, int64_t ldg, void *pack,
+                           void *stream);
+int ctgcn_gat_bwd_row_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S, int64_t lds,
+                          const float *G, int64_t ldg, const float *v, const void *pack, double alpha, double p_att, uint64_t key, float *R,
+                          int64_t ldr, float *csum, float *du, const int32_t *long_rows, int32_t n_long, int32_t long_threshold,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_gat_bwd_col_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *G, int64_t ldg,
+                          const float *S, int64_t lds, const float *v, const void *pack, const float *a_src, const float *a_dst, double alpha,
+                          double p_att, uint64_t key, const float *du, float *dS, int64_t ldds, float *B, int64_t ldb, float *ksum, float *dv,
+                          const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
