@@ -172,6 +172,19 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "ctgcn_gat_bwd_col_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _c.c_double, _c.c_double, _c.c_uint64,
                                      _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_pool_conv_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _i64, _i32, _c.c_double, _c.c_uint64,
+                                       _vp, _vp, _i64, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_pool_prep_workspace_bytes": (_sz, [_i64, _i32]),
+    "ctgcn_pool_conv_prep_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _c.c_double, _c.c_uint64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ctgcn_pool_max_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_pool_max_bwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_bn_stats_rows": (_i32, []),
+    "ctgcn_bn_stats_workspace_bytes": (_sz, [_i64, _i32]),
+    "ctgcn_bn_stats_f32": (_int, [_i64, _i32, _vp, _i64, _c.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_bn_apply_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _c.c_double, _c.c_uint64, _vp, _i64, _vp]),
+    "ctgcn_bn_bwd_workspace_bytes": (_sz, [_i64, _i32]),
+    "ctgcn_bn_bwd_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _c.c_double, _c.c_uint64, _i32, _vp, _i64, _vp, _vp,
+                                _vp, _sz, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

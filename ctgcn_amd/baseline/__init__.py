@@ -3,3 +3,5 @@ from .egcn import EvolveGCN  # noqa: F401
 from .gat import GAT, SpGraphAttentionLayer  # noqa: F401
 from .gcn import GCN, GraphConvolution  # noqa: F401
 from .gcrn import GCRN  # noqa: F401
+from .gin import GIN  # noqa: F401
+from .sage import SAGE, SAGE_Layer, Aggregator  # noqa: F401

@@ -24,7 +24,18 @@ from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLo
                       epoch_batch_seed)
 
 _S_MODELS = ('CGCN-S', 'CTGCN-S')
-_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT')      # the baselines: single-output, trained like the -C models
+_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT', 'GIN', 'SAGE')      # the baselines: single-output, trained like the -C models
+
+
+def _check_own_baseline(trainer, model, name):
+    """GIN and SAGE are trained as this package's own modules, whose pooling runs in ctgcn_pool.hip.  Another module that carries the name
+    (the reference's classes with their dense masks and Python loops, or a model relabelled by hand) has no such path and is refused,
+    not run through whatever forward it happens to have."""
+    if name in ('GIN', 'SAGE'):
+        from . import baseline
+        cls = getattr(baseline, name)
+        if not isinstance(model, cls):
+            raise NotImplementedError("%s trains %s as ctgcn_amd.baseline.%s, got %s" % (trainer, name, name, type(model).__name__))
 
 
 def batch_count(node_num, batch_size):
@@ -88,6 +99,7 @@ class UnsupervisedEmbedding(object):
         name = getattr(model, 'method_name', None)
         if name not in _SUPPORTED:
             raise NotImplementedError("UnsupervisedEmbedding covers %s, not %r" % (', '.join(_SUPPORTED), name))
+        _check_own_baseline("UnsupervisedEmbedding", model, name)
         want = ReconstructionLoss if name in _S_MODELS else NegativeSamplingLoss
         if not isinstance(self.loss, want):
             raise ValueError("%s trains with %s, got %s" % (name, want.__name__, type(self.loss).__name__))
@@ -341,6 +353,7 @@ class SupervisedEmbedding(object):
         name = getattr(model, 'method_name', None)
         if name not in _SUPPORTED:
             raise NotImplementedError("SupervisedEmbedding covers %s, not %r" % (', '.join(_SUPPORTED), name))
+        _check_own_baseline("SupervisedEmbedding", model, name)
         want = StructureClassificationLoss if name in _S_MODELS else ClassificationLoss
         if not isinstance(self.loss, want):
             raise ValueError("%s trains with %s, got %s" % (name, want.__name__, type(self.loss).__name__))

@@ -95,6 +95,48 @@ def as_gcn_adj(adj, device, symmetric=True):
     return hit[0]
 
 
+def as_pool_adj(adj, kind, self_loop=False):
+    """The matrix a GIN / GraphSAGE pooling step reads, derived from a GcnAdj once and cached on it (so it lives exactly as long as
+    the as_gcn_adj entry it came from).  kind:
+      'sum', 'average'                   the raw adjacency's weights, plus a unit diagonal with self_loop (added to a stored one); 'average'
+                                         divides each row by its weighted sum (ops.gcn_normalize(row_norm=True); an empty row stays 0)
+      'pattern-sum', 'pattern-average'   the pattern alone: values 1, or 1 / the number of entries; with self_loop the node joins its
+                                         own set, as a set (a stored self loop is not counted twice)"""
+    cache = adj.__dict__.setdefault("_pool", {})
+    hit = cache.get((kind, bool(self_loop)))
+    if hit is not None:
+        return hit
+    n, dev = adj.n, adj.device
+    rows, cols = adj._rows(), adj.col.to(torch.int64)
+    eye = torch.arange(n, device=dev)
+    if kind in ("sum", "average"):
+        vals = adj.val
+        if self_loop:
+            rows, cols, vals = torch.cat((rows, eye)), torch.cat((cols, eye)), torch.cat((vals, torch.ones(n, device=dev)))
+        t = torch.sparse_coo_tensor(torch.stack((rows, cols)), vals, torch.Size((n, n)))
+        out = ops.GcnAdj.from_sparse_tensor(t, dev, long_threshold=adj.long_threshold, check_symmetric=False)
+        if kind == "average":
+            out.val = ops.gcn_normalize(out.row_ptr, out.col, out.val, row_norm=True)
+    elif kind in ("pattern-sum", "pattern-average"):
+        keys = rows * n + cols
+        if self_loop:
+            keys = torch.unique(torch.cat((keys, eye * (n + 1))))
+        else:
+            keys = torch.unique(keys)                              # sorted: row-major order, columns ascending
+        rows, cols = torch.div(keys, n, rounding_mode="floor"), keys % n
+        counts = torch.bincount(rows, minlength=n)
+        row_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        row_ptr[1:] = counts.cumsum(0)
+        vals = torch.ones(keys.numel(), dtype=torch.float32, device=dev)
+        if kind == "pattern-average":
+            vals = (1.0 / counts.to(torch.float64))[rows].to(torch.float32)
+        out = ops.GcnAdj(row_ptr.to(torch.int32), cols.to(torch.int32), vals, adj.long_threshold)
+    else:
+        raise ValueError("unknown pooling matrix %r" % (kind,))
+    cache[kind, bool(self_loop)] = out
+    return out
+
+
 _identity_cache = {}
 
 

@@ -2349,3 +2349,264 @@ def gat_conv(S, a_src, a_dst, adj, heads, alpha=0.2, epi=GAT_EPI_NONE, p_att=0.0
     mask = 2 ** 64 - 1
     return _GatConv.apply(_row_view(S), a_src.contiguous(), a_dst.contiguous(), adj, heads, alpha, int(epi), p_att, int(key) & mask, p_feat,
                           int(fkey) & mask)
+
+
+# ------------------------------------------------------------------------- pooling layers of the GIN / GraphSAGE baselines (ctgcn_pool.hip)
+POOL_EPI_NONE, POOL_EPI_NORM = 0, 1
+
+
+def _pool_conv_fwd(adj, S, T, self_scale, bias, epi, p=0.0, key=0, out=None):
+    """(Y, norm or None, Ysave or None): ctgcn_pool_conv_fwd_f32.  adj None: no matrix, the epilogue of T alone.  Ysave: with dropout
+    the normalised rows before it (what the backward reads); Y itself otherwise."""
+    lib = _lib.load()
+    n, d = (T if S is None else S).shape
+    dev = (T if S is None else S).device
+    Y = torch.empty(n, d, dtype=torch.float32, device=dev) if out is None else out
+    norm = torch.empty(n, dtype=torch.float32, device=dev) if epi == POOL_EPI_NORM else None
+    save = torch.empty(n, d, dtype=torch.float32, device=dev) if (epi == POOL_EPI_NORM and p > 0) else None
+    matrix = (None, None, None) if adj is None else (ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val))
+    long = (None, 0, 1, None, 0) if adj is None else _gcn_long(adj, d)
+    with torch.cuda.device(dev), _timed("pool_conv_fwd", n=n, d=d, nnz=0 if adj is None else adj.nnz):
+        check(lib.ctgcn_pool_conv_fwd_f32(n, d, *matrix, ptr(S), 0 if S is None else S.stride(0), ptr(T), 0 if T is None else T.stride(0),
+                                          float(self_scale), ptr(bias), ptr(Y), Y.stride(0), epi, p, key, ptr(norm), ptr(save),
+                                          0 if save is None else save.stride(0), *long, _stream()), "ctgcn_pool_conv_fwd_f32")
+    return Y, norm, (Y if save is None else save)
+
+
+def _pool_conv_prep(dY, Ysave, norm, p=0.0, key=0, want_db=False, out=None):
+    """(G, db): ctgcn_pool_conv_prep_f32, the pre-pass of POOL_EPI_NORM.  G is written to out when given; db None unless wanted."""
+    lib = _lib.load()
+    n, d = dY.shape
+    dev = dY.device
+    G = torch.empty(n, d, dtype=torch.float32, device=dev) if out is None else out
+    db = torch.zeros(d, dtype=torch.float32, device=dev) if want_db else None
+    nbytes = int(lib.ctgcn_pool_prep_workspace_bytes(n, d)) if want_db else 0
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if want_db else None
+    with torch.cuda.device(dev), _timed("pool_conv_prep", n=n, d=d):
+        check(lib.ctgcn_pool_conv_prep_f32(n, d, ptr(dY), dY.stride(0), ptr(Ysave), Ysave.stride(0), ptr(norm), p, key, ptr(G), G.stride(0),
+                                           ptr(db), ptr(ws), nbytes, _stream()), "ctgcn_pool_conv_prep_f32")
+    return G, db
+
+
+class _PoolConv(torch.autograd.Function):
+    """S, T: [n, d] or None.  pair: S is Z [n, 2 d] = [T | S], whose gradient is written as one buffer."""
+
+    @staticmethod
+    def forward(ctx, S, T, scale_t, bias, adj, scale, epi, p, key, pair):
+        if pair:
+            d = S.shape[1] // 2
+            Y, norm, save = _pool_conv_fwd(adj, S[:, d:], S[:, :d], scale, bias, epi, p, key)
+        else:
+            Y, norm, save = _pool_conv_fwd(adj, S, T, scale, bias, epi, p, key)
+        ctx.adj, ctx.scale, ctx.epi, ctx.p, ctx.key, ctx.pair = adj, scale, epi, p, key, pair
+        ctx.has_T = T is not None
+        need_T = ctx.has_T and scale_t is not None
+        ctx.save_for_backward(*((save, norm) if epi == POOL_EPI_NORM else ()), *((T,) if need_T else ()))
+        ctx.saved_T = need_T
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        saved = ctx.saved_tensors
+        need_S, need_T, need_scale, need_b = ctx.needs_input_grad[:4]
+        dY = _row_view(dY)
+        n, d = dY.shape
+        dZ = torch.empty(n, 2 * d, dtype=torch.float32, device=dY.device) if ctx.pair else None
+        direct = ctx.pair and ctx.scale == 1.0                       # dT = G: the pre-pass writes it in place
+        if ctx.epi == POOL_EPI_NORM:
+            G, db = _pool_conv_prep(dY, saved[0], saved[1], ctx.p, ctx.key, want_db=need_b, out=dZ[:, :d] if direct else None)
+        else:
+            G, db = _gcn_conv_prep(dY, None, None, GCN_EPI_NONE, want_db=need_b)
+            if direct:
+                dZ[:, :d].copy_(G)
+        d_scale = (G * saved[-1]).sum() if (need_scale and ctx.saved_T) else None
+        if ctx.pair:
+            if not direct:
+                torch.mul(G, ctx.scale, out=dZ[:, :d])
+            _gcn_conv_fwd(ctx.adj.transposed(), G, None, GCN_EPI_NONE, out=dZ[:, d:])
+            return dZ, None, d_scale, db, None, None, None, None, None, None
+        dS = _gcn_conv_fwd(ctx.adj.transposed(), G, None, GCN_EPI_NONE)[0] if (need_S and ctx.adj is not None) else None
+        dT = (G if ctx.scale == 1.0 else G * ctx.scale) if (need_T and ctx.has_T) else None
+        return dS, dT, d_scale, db, None, None, None, None, None, None
+
+
+def pool_conv(S, adj, T=None, self_scale=1.0, bias=None, epi=POOL_EPI_NONE, p=0.0, key=0):
+    """Y = epi(Â S + self_scale T + bias) for any GcnAdj, differentiable in S, T, bias and (when it is a tensor) self_scale.  T [n, d]
+    may be S itself, have its own row stride, or be another column slice of S's buffer; S = None with adj = None is the epilogue of
+    self_scale T + bias alone.  epi: POOL_EPI_NONE, or POOL_EPI_NORM: ReLU, then F.normalize(p=2) over each row, then dropout with
+    probability p when p > 0 (entry (i, c) kept iff u01(key, i, c) >= p, scaled by 1 / (1 - p)).  One pass is a GraphSAGE layer after
+    its product, S and T the two halves of h [W_self ; W_neigh]^T.  The backward is one N x d pre-pass (the gradient before the epilogue
+    and the bias gradient), dT = self_scale G and the plain aggregation dS = Â^T G over adj.transposed().
+    A tensor self_scale is read back to the host (one device synchronisation per call): the kernel takes the scale by value."""
+    if (S is None) != (adj is None):
+        raise ValueError("S and adj go together")
+    if S is None and T is None:
+        raise ValueError("nothing to pool: S and T are both None")
+    _need_cuda(S, T, bias, None if adj is None else adj.val)
+    if epi not in (POOL_EPI_NONE, POOL_EPI_NORM):
+        raise ValueError("epi must be POOL_EPI_NONE or POOL_EPI_NORM")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p must lie in [0, 1), got %r" % p)
+    first = T if S is None else S
+    n = first.shape[0] if adj is None else adj.n
+    for name, t in (("S", S), ("T", T)):
+        if t is not None and (t.dim() != 2 or tuple(t.shape) != (n, first.shape[1])):
+            raise ValueError("%s must be [%d, %d], got %s" % (name, n, first.shape[1], tuple(t.shape)))
+    if any(t is not None and t.dtype != torch.float32 for t in (S, T, bias)):
+        raise TypeError("fp32 features and bias expected")
+    if any(t is not None and t.device != first.device for t in (S, T, bias)) or (adj is not None and adj.device != first.device):
+        raise ValueError("S, T, bias and the adjacency must be on one device")
+    if bias is not None and tuple(bias.shape) != (first.shape[1],):
+        raise ValueError("bias must have %d entries" % first.shape[1])
+    scale_t = self_scale if isinstance(self_scale, torch.Tensor) else None
+    scale = float(self_scale if scale_t is None else scale_t.detach())
+    key = int(key) & (2 ** 64 - 1)
+    bias = None if bias is None else bias.contiguous()
+    # the two halves of one [n, 2 d] buffer as [T | S]: the gradient is assembled in one buffer, with no zero-padded halves to add
+    if (scale_t is None and S is not None and T is not None and S is not T and S._base is not None and S._base is T._base
+            and S._base.dim() == 2 and S._base.is_contiguous() and tuple(S._base.shape) == (n, 2 * S.shape[1])
+            and T.storage_offset() == S._base.storage_offset()
+            and S.storage_offset() == T.storage_offset() + S.shape[1] and S.stride() == T.stride() == S._base.stride()):
+        return _PoolConv.apply(S._base, None, scale_t, bias, adj, scale, int(epi), p, key, True)
+    return _PoolConv.apply(None if S is None else _row_view(S), None if T is None else _row_view(T), scale_t, bias, adj, scale, int(epi), p, key,
+                           False)
+
+
+def _pool_max_fwd(adj, S):
+    """(Y, arg int32 [n, d]): ctgcn_pool_max_fwd_f32"""
+    lib = _lib.load()
+    n, d = S.shape
+    Y = torch.empty(n, d, dtype=torch.float32, device=S.device)
+    arg = torch.empty(n, d, dtype=torch.int32, device=S.device)
+    long = _gcn_long(adj, 2 * ((d + 3) // 4 * 4))                    # a partial maximum and its index per column
+    with torch.cuda.device(S.device), _timed("pool_max_fwd", n=n, d=d, nnz=adj.nnz):
+        check(lib.ctgcn_pool_max_fwd_f32(n, d, ptr(adj.row_ptr), ptr(adj.col), ptr(S), S.stride(0), ptr(Y), Y.stride(0), ptr(arg), arg.stride(0),
+                                         *long, _stream()), "ctgcn_pool_max_fwd_f32")
+    return Y, arg
+
+
+def _pool_max_bwd(adj_t, dY, arg):
+    """dS: ctgcn_pool_max_bwd_f32 over the transposed GcnAdj"""
+    lib = _lib.load()
+    n, d = dY.shape
+    dS = torch.empty(n, d, dtype=torch.float32, device=dY.device)
+    with torch.cuda.device(dY.device), _timed("pool_max_bwd", n=n, d=d, nnz=adj_t.nnz):
+        check(lib.ctgcn_pool_max_bwd_f32(n, d, ptr(adj_t.row_ptr), ptr(adj_t.col), ptr(dY), dY.stride(0), ptr(arg), arg.stride(0), ptr(dS),
+                                         dS.stride(0), *_gcn_long(adj_t, d), _stream()), "ctgcn_pool_max_bwd_f32")
+    return dS
+
+
+class _PoolMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, adj):
+        Y, arg = _pool_max_fwd(adj, S)
+        ctx.adj = adj
+        ctx.save_for_backward(arg)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        return _pool_max_bwd(ctx.adj.transposed(), _row_view(dY), ctx.saved_tensors[0]), None
+
+
+def pool_max(S, adj):
+    """Y[i, c] = max over the stored entries j of row i of S[j, c] (the pattern alone: values are not read), zeros for an empty row;
+    differentiable in S.  Among equal values the lowest column index wins, and the gradient goes there alone: the backward pulls
+    dS[j, c] = sum_i [arg[i, c] == j] dY[i, c] over adj.transposed() in ascending i.  Inputs are finite."""
+    _need_cuda(S, adj.val)
+    if S.dim() != 2 or S.shape[0] != adj.n:
+        raise ValueError("S must be [%d, d], got %s" % (adj.n, tuple(S.shape)))
+    if S.dtype != torch.float32:
+        raise TypeError("fp32 features expected")
+    if S.device != adj.device:
+        raise ValueError("S on %s but adjacency on %s" % (S.device, adj.device))
+    return _PoolMax.apply(_row_view(S), adj)
+
+
+def _bn_stats(x, eps):
+    """(mean, biased var, rstd), each [d]: ctgcn_bn_stats_f32"""
+    lib = _lib.load()
+    n, d = x.shape
+    mean, var, rstd = (torch.empty(d, dtype=torch.float32, device=x.device) for _ in range(3))
+    nbytes = int(lib.ctgcn_bn_stats_workspace_bytes(n, d))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device), _timed("bn_stats", n=n, d=d):
+        check(lib.ctgcn_bn_stats_f32(n, d, ptr(x), x.stride(0), eps, ptr(mean), ptr(var), ptr(rstd), ptr(ws), nbytes, _stream()), "ctgcn_bn_stats_f32")
+    return mean, var, rstd
+
+
+def _bn_apply(x, mean, rstd, weight, bias, relu, p=0.0, key=0):
+    lib = _lib.load()
+    n, d = x.shape
+    y = torch.empty(n, d, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed("bn_apply", n=n, d=d):
+        check(lib.ctgcn_bn_apply_f32(n, d, ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(weight), ptr(bias), 1 if relu else 0, p, key, ptr(y),
+                                     y.stride(0), _stream()), "ctgcn_bn_apply_f32")
+    return y
+
+
+def _bn_bwd(x, dy, mean, rstd, weight, bias, relu, p, key, batch_stats, need_dx=True):
+    """(dx or None, dw, db): ctgcn_bn_bwd_f32"""
+    lib = _lib.load()
+    n, d = x.shape
+    dev = x.device
+    dx = torch.empty(n, d, dtype=torch.float32, device=dev) if need_dx else None
+    dw, db = torch.empty(d, dtype=torch.float32, device=dev), torch.empty(d, dtype=torch.float32, device=dev)
+    nbytes = int(lib.ctgcn_bn_bwd_workspace_bytes(n, d))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _timed("bn_bwd", n=n, d=d):
+        check(lib.ctgcn_bn_bwd_f32(n, d, ptr(x), x.stride(0), ptr(dy), dy.stride(0), ptr(mean), ptr(rstd), ptr(weight), ptr(bias),
+                                   1 if relu else 0, p, key, 1 if batch_stats else 0, ptr(dx), 0 if dx is None else dx.stride(0), ptr(dw), ptr(db),
+                                   ptr(ws), nbytes, _stream()), "ctgcn_bn_bwd_f32")
+    return dx, dw, db
+
+
+class _BatchNormAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, mean, var, relu, p, key, eps):
+        batch_stats = mean is None
+        if batch_stats:
+            mean, var, rstd = _bn_stats(x, eps)
+        else:
+            rstd = torch.rsqrt(var.double() + eps).float()
+        y = _bn_apply(x, mean, rstd, weight, bias, relu, p, key)
+        ctx.relu, ctx.p, ctx.key, ctx.batch_stats = relu, p, key, batch_stats
+        ctx.save_for_backward(x, mean, rstd, weight, bias)
+        ctx.mark_non_differentiable(mean, var)
+        return y, mean, var
+
+    @staticmethod
+    def backward(ctx, dy, *_):
+        x, mean, rstd, weight, bias = ctx.saved_tensors
+        dx, dw, db = _bn_bwd(x, _row_view(dy), mean, rstd, weight, bias, ctx.relu, ctx.p, ctx.key, ctx.batch_stats, ctx.needs_input_grad[0])
+        return dx, dw, db, None, None, None, None, None, None
+
+
+def batch_norm_act(x, weight, bias, mean=None, var=None, relu=True, p=0.0, key=0, eps=1e-5):
+    """(y, mean, var) with y = dropout(relu((x - mean) / sqrt(var + eps) * weight + bias)) over the columns of x [n, d], differentiable
+    in x, weight and bias.  mean / var None (training mode): the batch's own mean and biased variance, computed in fp64 and returned
+    for the running buffers; a single row raises torch's ValueError.  Given (eval mode): used as constants.  relu False leaves the ReLU
+    out; dropout as in gcn_conv (entry (i, c) kept iff u01(key, i, c) >= p).  The backward keeps x, mean and rstd alone: the ReLU mask
+    and the draw are made again."""
+    _need_cuda(x, weight, bias, mean, var)
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("x must be [n, d], got %s" % (tuple(x.shape),))
+    d = x.shape[1]
+    if (mean is None) != (var is None):
+        raise ValueError("mean and var go together")
+    for name, t in (("weight", weight), ("bias", bias), ("mean", mean), ("var", var)):
+        if t is not None and (tuple(t.shape) != (d,) or t.dtype != torch.float32 or t.device != x.device):
+            raise ValueError("%s must be an fp32 [%d] vector on %s" % (name, d, x.device))
+    if x.dtype != torch.float32:
+        raise TypeError("fp32 features expected")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p must lie in [0, 1), got %r" % p)
+    if mean is None and x.shape[0] == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (x.shape,))
+    if x.shape[0] == 0:
+        raise ValueError("batch_norm_act needs at least one row")
+    mean = None if mean is None else mean.detach().contiguous()
+    var = None if var is None else var.detach().contiguous()
+    return _BatchNormAct.apply(_row_view(x), weight.contiguous(), bias.contiguous(), mean, var, bool(relu), p, int(key) & (2 ** 64 - 1), float(eps))

@@ -961,6 +961,65 @@ int ctgcn_gat_bwd_col_f32(int64_t n, int32_t d, int32_t heads, const int32_t *ro
                           const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
                           void *stream);
 
+/*
+ * Pooling layers of the GIN and GraphSAGE baselines (reference baseline/gin.py, baseline/sage.py; ctgcn_amd/baseline/gin.py, sage.py),
+ * ctgcn_pool.hip.  Same CSR and long-row rules as ctgcn_gcn_conv_fwd_f32; the matrix need not be symmetric.
+ *
+ * ctgcn_pool_conv_fwd_f32: Y[i] = epi(Σ_e val[e] · S[col[e]] + self_scale · T[i] + bias).  T [n, d] (row stride ldt) and bias [d] may
+ *   be null; T may be S itself or another column slice of S's buffer.  row_ptr null: no matrix (every row empty; col, val, S unused).
+ *   epi 0 none; 1 ReLU, then the row's L2 normalisation x / max(‖x‖₂, 1e-12) with norm[i] = ‖x‖₂ (norm required), then dropout when
+ *   p > 0: entry (i, c) kept iff u01(key, i, c) >= p and scaled by 1 / (1 - p).  With p > 0 Ysave [n, d], when not null, receives the
+ *   normalised rows before dropout, which the backward reads (with p = 0 that is Y).
+ * ctgcn_pool_conv_prep_f32: the backward's N x d pass of epi 1.  g = dY through the dropout draw (made again from key), then
+ *   G = Y > 0 ? (g − Y ⟨Y, g⟩) / norm : 0 where norm >= 1e-12, else Y > 0 ? g / 1e-12 : 0; Y the normalised rows before dropout.
+ *   db [d], when not null, receives Σ_i G[i]: per-block partial sums in the workspace (ctgcn_pool_prep_workspace_bytes(n, d) bytes,
+ *   16-byte aligned), added in block order by a second launch.  Then dT = self_scale · G and dS = Âᵀ G (ctgcn_gcn_conv_fwd_f32 over
+ *   the transposed CSR).
+ * ctgcn_pool_max_fwd_f32: Y[i, c] = max_e S[col[e], c] and arg[i, c] = the col[e] that holds it, the lowest among equal values; an
+ *   empty row gives 0 and -1.  The values of the matrix are not read.  Long rows: workspace of n_long · pieces · round_up(d, 4) · 8
+ *   bytes (the partial maxima and their indices).
+ * ctgcn_pool_max_bwd_f32: over the transposed CSR (row_ptr / col / long rows of Aᵀ): dS[j, c] = Σ_{i in row j of Aᵀ} [arg[i, c] == j] ·
+ *   dY[i, c], in the stored (ascending) order of i.  Long rows: workspace of n_long · pieces · round_up(d, 4) · 4 bytes.
+ * ctgcn_bn_stats_f32: per-column mean, biased variance and rstd = 1 / sqrt(var + eps) over the n >= 1 rows of x.  Blocks of
+ *   ctgcn_bn_stats_rows() rows sum x − K and (x − K)² in fp64 (K the block's first row) into a (mean, M2) pair per block and column
+ *   in the workspace (ctgcn_bn_stats_workspace_bytes(n, d) bytes, 8-byte aligned); a second launch merges the pairs by Chan's
+ *   formula in fp64 in a fixed order.
+ * ctgcn_bn_apply_f32: y = dropout(relu((x − mean) · rstd · weight + bias)); relu 0 or 1, dropout as above when p > 0.
+ * ctgcn_bn_bwd_f32: g = dy through the dropout draw and the ReLU mask, both made again from x; db = Σ_i g, dw = Σ_i g ⊙ x̂ as per-block
+ *   column sums added in block order (workspace of ctgcn_bn_bwd_workspace_bytes(n, d) bytes, 16-byte aligned); then, when dx is not
+ *   null, dx = weight · rstd · (g − db / n − x̂ · dw / n) with batch_stats 1, weight · rstd · g with 0 (statistics given, eval mode).
+ * float4 rows when d, every leading dimension and every base address allow it, scalar rows otherwise.
+ * Returns CTGCN_E_INVALID for null pointers, n < 0 or n >= 2^31, d < 1, a leading dimension below d or a p outside [0, 1);
+ * CTGCN_E_WORKSPACE for a workspace that is too small; 0 for n = 0 (ctgcn_bn_stats_f32 needs n >= 1).
+ * CTGCN_E_UNSUPPORTED for more than 65535 long rows in the three gather entries (raise long_threshold), for more than 65535 statistics
+ * blocks in ctgcn_bn_stats_f32 (n above 65535 · ctgcn_bn_stats_rows() = 8 388 480 rows), and for n · d beyond a grid of 2^31 − 1 blocks
+ * of 256 in the apply and backward passes.
+ * No atomics; every sum has a fixed order: repeated calls on the same inputs are bit-identical.
+ */
+int ctgcn_pool_conv_fwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val, const float *S, int64_t lds,
+                            const float *T, int64_t ldt, float self_scale, const float *bias, float *Y, int64_t ldy, int32_t epi, double p,
+                            uint64_t key, float *norm, float *Ysave, int64_t ldsave, const int32_t *long_rows, int32_t n_long,
+                            int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_pool_prep_workspace_bytes(int64_t n, int32_t d);
+int ctgcn_pool_conv_prep_f32(int64_t n, int32_t d, const float *dY, int64_t lddy, const float *Y, int64_t ldy, const float *norm, double p,
+                             uint64_t key, float *G, int64_t ldg, float *db, void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_pool_max_fwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *S, int64_t lds, float *Y,
+                           int64_t ldy, int32_t *arg, int64_t ldarg, const int32_t *long_rows, int32_t n_long, int32_t long_threshold,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_pool_max_bwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *dY, int64_t lddy,
+                           const int32_t *arg, int64_t ldarg, float *dS, int64_t ldds, const int32_t *long_rows, int32_t n_long,
+                           int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream);
+int32_t ctgcn_bn_stats_rows(void);
+size_t ctgcn_bn_stats_workspace_bytes(int64_t n, int32_t d);
+int ctgcn_bn_stats_f32(int64_t n, int32_t d, const float *x, int64_t ldx, double eps, float *mean, float *var, float *rstd, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int ctgcn_bn_apply_f32(int64_t n, int32_t d, const float *x, int64_t ldx, const float *mean, const float *rstd, const float *weight,
+                       const float *bias, int32_t relu, double p, uint64_t key, float *y, int64_t ldy, void *stream);
+size_t ctgcn_bn_bwd_workspace_bytes(int64_t n, int32_t d);
+int ctgcn_bn_bwd_f32(int64_t n, int32_t d, const float *x, int64_t ldx, const float *dy, int64_t lddy, const float *mean, const float *rstd,
+                     const float *weight, const float *bias, int32_t relu, double p, uint64_t key, int32_t batch_stats, float *dx,
+                     int64_t lddx, float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
