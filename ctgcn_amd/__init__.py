@@ -12,10 +12,11 @@ from .models import CDN, CGCN, CTGCN, EdgeClassifier, InnerProduct, MLPClassifie
 from .helper import DataLoader  # noqa: F401
 from .metrics import ClassificationLoss, NegativeSamplingLoss, ReconstructionLoss, StructureClassificationLoss  # noqa: F401
 from .embedding import SupervisedEmbedding, UnsupervisedEmbedding  # noqa: F401
-from .baseline import GAT, GCN, GCRN, GIN, SAGE, Aggregator, EvolveGCN, GraphConvolution, SAGE_Layer, SpGraphAttentionLayer  # noqa: F401
+from .baseline import (GAT, GCN, GCRN, GIN, PGNN, SAGE, Aggregator, EvolveGCN, GraphConvolution, Nonlinear, PGNN_layer,  # noqa: F401
+                       SAGE_Layer, SpGraphAttentionLayer)
 from .evaluation import DataGenerator, LinkPredictor, aggregate_results, evaluate, evaluate_window, link_prediction  # noqa: F401
 
 __all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoader", "NegativeSamplingLoss", "ReconstructionLoss",
            "UnsupervisedEmbedding", "SupervisedEmbedding", "MLPClassifier", "InnerProduct", "EdgeClassifier", "ClassificationLoss",
            "StructureClassificationLoss", "DataGenerator", "LinkPredictor", "aggregate_results", "evaluate", "evaluate_window", "link_prediction", "EvolveGCN",
-           "GCN", "GraphConvolution", "GCRN", "GAT", "SpGraphAttentionLayer", "GIN", "SAGE", "SAGE_Layer", "Aggregator"]
+           "GCN", "GraphConvolution", "GCRN", "GAT", "SpGraphAttentionLayer", "GIN", "SAGE", "SAGE_Layer", "Aggregator", "PGNN", "PGNN_layer", "Nonlinear"]

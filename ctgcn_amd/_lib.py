@@ -185,6 +185,18 @@ SIGNATURES = {
     "ctgcn_bn_bwd_workspace_bytes": (_sz, [_i64, _i32]),
     "ctgcn_bn_bwd_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _c.c_double, _c.c_uint64, _i32, _vp, _i64, _vp, _vp,
                                 _vp, _sz, _vp]),
+    "ctgcn_pgnn_dist_workspace_bytes": (_sz, []),
+    "ctgcn_pgnn_anchor_dist": (_int, [_i64, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _c.POINTER(_i32), _vp, _sz, _vp]),
+    "ctgcn_pgnn_conv_fwd_f32": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _c.c_double,
+                                       _c.c_uint64, _vp]),
+    "ctgcn_pgnn_bwd_row_workspace_bytes": (_sz, [_i64, _i32]),
+    "ctgcn_pgnn_conv_bwd_row_f32": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _c.c_double,
+                                           _c.c_uint64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_pgnn_bwd_pull_workspace_bytes": (_sz, [_i64, _i32]),
+    "ctgcn_pgnn_conv_bwd_pull_f32": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64,
+                                            _i64, _vp, _i64, _vp, _sz, _vp]),
+    "ctgcn_pgnn_table_grad_workspace_bytes": (_sz, [_i64]),
+    "ctgcn_pgnn_table_grad_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

@@ -4,4 +4,6 @@ from .gat import GAT, SpGraphAttentionLayer  # noqa: F401
 from .gcn import GCN, GraphConvolution  # noqa: F401
 from .gcrn import GCRN  # noqa: F401
 from .gin import GIN  # noqa: F401
+from .pgnn import (PGNN, Nonlinear, PGNN_layer, anchor_set_count, get_dist_max, get_random_anchorset,  # noqa: F401
+                   precompute_dist_data, preselect_anchor)
 from .sage import SAGE, SAGE_Layer, Aggregator  # noqa: F401

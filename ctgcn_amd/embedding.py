@@ -1,5 +1,5 @@
 """UnsupervisedEmbedding: the reference's unsupervised trainer (reference embedding.py:13-89, 293-368) for CTGCN-C/-S, CGCN-C/-S and the
-EvolveGCN and GCRN baselines (single-output models: trained like the -C models).
+EvolveGCN, GCRN, GAT, GIN, SAGE and PGNN baselines (single-output models: trained like the -C models).
 
 The reference runs, per epoch, one full-graph forward + loss(batch) + backward for each of the ceil(N / batch_size) batches of a
 shuffled node order and steps Adam once after the last batch (gradient accumulation).  The weights do not change inside an epoch
@@ -8,6 +8,11 @@ and the forward is deterministic, so every batch sees the same embeddings and th
 d(Σ loss)/d(output) come from the kernels of ctgcn_epoch.hip (metrics.*.epoch_loss).  fused=False is the reference's loop step
 for step.  Both modes draw the same samples: batch b of epoch e, snapshot t uses metrics.epoch_batch_seed(base, e, b, t), and the
 node order is the reference's all_nodes[torch.randperm(N)] from torch's CPU generator.
+
+A PGNN takes (x_list, dists_max, dists_argmax), drawn by baseline.pgnn.preselect_anchor from node_dist_list before each forward, as the
+reference's get_model_res does.  The fused epoch makes one forward per epoch and so draws anchor sets once per epoch; fused=False draws
+them per batch, as the reference does.  Under torch.manual_seed the fused paths repeat a run bit for bit; the unfused paths gather rows
+with torch's indexing, whose backward adds with float atomics, and repeat bit for bit under torch.use_deterministic_algorithms(True).
 
 SupervisedEmbedding is the reference's supervised trainer (embedding.py:93-290) for the learning types S-node, S-edge, S-link-st
 and S-link-dy on the same models; its classifier head and loss run the kernels of ctgcn_supervised.hip.
@@ -24,18 +29,33 @@ from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLo
                       epoch_batch_seed)
 
 _S_MODELS = ('CGCN-S', 'CTGCN-S')
-_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT', 'GIN', 'SAGE')      # the baselines: single-output, trained like the -C models
+_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT', 'GIN', 'SAGE', 'PGNN')      # the baselines: single-output, trained like the -C models
 
 
 def _check_own_baseline(trainer, model, name):
-    """GIN and SAGE are trained as this package's own modules, whose pooling runs in ctgcn_pool.hip.  Another module that carries the name
-    (the reference's classes with their dense masks and Python loops, or a model relabelled by hand) has no such path and is refused,
-    not run through whatever forward it happens to have."""
-    if name in ('GIN', 'SAGE'):
+    """GIN, SAGE and PGNN are trained as this package's own modules, whose passes run in ctgcn_pool.hip and ctgcn_pgnn.hip.  Another module
+    that carries the name (the reference's classes with their dense masks and Python loops, or a model relabelled by hand) has no such
+    path and is refused, not run through whatever forward it happens to have."""
+    if name in ('GIN', 'SAGE', 'PGNN'):
         from . import baseline
         cls = getattr(baseline, name)
         if not isinstance(model, cls):
             raise NotImplementedError("%s trains %s as ctgcn_amd.baseline.%s, got %s" % (trainer, name, name, type(model).__name__))
+
+
+def model_forward(model, x_list, adj_list, node_dist_list, node_num, device):
+    """model(x_list, adj_list), or for a PGNN one draw of anchor sets and model(x_list, dists_max, dists_argmax) (reference
+    embedding.py:209-212); dist_argmax holds node ids when the model carries anchor_node_ids = True"""
+    if getattr(model, 'method_name', None) != 'PGNN':
+        return model(x_list, adj_list)
+    from .baseline.pgnn import preselect_anchor
+    dists_max, dists_argmax = preselect_anchor(node_num, node_dist_list, device, node_ids=bool(getattr(model, 'anchor_node_ids', False)))
+    return model(x_list, dists_max, dists_argmax)
+
+
+def _check_node_dist(name, node_dist_list):
+    if name == 'PGNN' and node_dist_list is None:
+        raise ValueError("a PGNN needs node_dist_list (baseline.pgnn.precompute_dist_data of the snapshots' edge lists)")
 
 
 def batch_count(node_num, batch_size):
@@ -118,8 +138,8 @@ class UnsupervisedEmbedding(object):
             return emb, struct, struct
         return res, None, res
 
-    def _epoch_fused(self, model, name, x_list, adj_list, node_indices, batch_size, epoch_idx, base):
-        res = model(x_list, adj_list)
+    def _epoch_fused(self, model, name, x_list, adj_list, node_indices, batch_size, epoch_idx, base, node_dist_list=None):
+        res = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device)
         emb, struct, output_list = self._split(name, res)
         B = batch_count(self.node_num, batch_size)
         if struct is None:
@@ -138,11 +158,11 @@ class UnsupervisedEmbedding(object):
         torch.autograd.backward([o for o, _ in pairs], [g for _, g in pairs])
         return losses.sum(0).tolist(), output_list
 
-    def _epoch_per_batch(self, model, name, x_list, adj_list, node_indices, batch_size, epoch_idx, base):
+    def _epoch_per_batch(self, model, name, x_list, adj_list, node_indices, batch_size, epoch_idx, base, node_dist_list=None):
         losses, output_list = [], None
         for j, (lo, hi) in enumerate(batch_bounds(self.node_num, batch_size)):
             batch_indices = node_indices[lo:hi]
-            res = model(x_list, adj_list)
+            res = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device)
             emb, struct, output_list = self._split(name, res)
             if struct is None:
                 T = len(emb) if isinstance(emb, list) or emb.dim() == 3 else 1
@@ -157,9 +177,11 @@ class UnsupervisedEmbedding(object):
 
     def learn_embedding(self, adj_list, x_list, edge_list=None, node_dist_list=None, epoch=50, batch_size=1024, lr=1e-3, start_idx=0,
                         weight_decay=0., model_file='ctgcn', load_model=False, shuffle=True, export=True, fused=True):
-        """reference embedding.py:329-368; edge_list / node_dist_list are the VGRNN / PGNN inputs and unused here."""
+        """reference embedding.py:329-368; edge_list is the VGRNN input and unused here; node_dist_list is what a PGNN draws its anchor
+        distances from (required for it, unused otherwise)."""
         model, loss_model, optimizer = self.prepare(load_model, model_file, lr=lr, weight_decay=weight_decay)
         name = self._check_model(model)
+        _check_node_dist(name, node_dist_list)
         all_nodes = torch.arange(self.node_num, device=self.device)
         base = self.sample_seed_base = self._seed_base()
         run = self._epoch_fused if fused else self._epoch_per_batch
@@ -169,7 +191,7 @@ class UnsupervisedEmbedding(object):
         for i in range(epoch):
             node_indices = all_nodes[epoch_order(self.node_num, shuffle).to(self.device)]
             t1 = time.time()
-            self.last_epoch_losses, output_list = run(model, name, x_list, adj_list, node_indices, batch_size, i, base)
+            self.last_epoch_losses, output_list = run(model, name, x_list, adj_list, node_indices, batch_size, i, base, node_dist_list)
             optimizer.step()            # gradient accumulation over the epoch's batches (embedding.py:349-352)
             model.zero_grad()
             print('epoch', i + 1, ', batches =', len(self.last_epoch_losses), ', loss:', sum(self.last_epoch_losses),
@@ -345,7 +367,7 @@ class SupervisedEmbedding(object):
             embedding_list = embedding_list[:-1] if learning_type == 'S-link-dy' else embedding_list
             cls_list = classifier(embedding_list, batch_indices)
             return [cls_list, embedding_list, structure_list], structure_list, hx
-        embedding_list = model(x_list, adj_list)
+        embedding_list = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device)
         embedding_list = embedding_list[:-1] if learning_type == 'S-link-dy' else embedding_list
         return classifier(embedding_list, batch_indices), embedding_list, hx
 
@@ -366,7 +388,7 @@ class SupervisedEmbedding(object):
         """reference embedding.py:230-290.  train_classifier departs from the reference (see the class).  batch_info: a precomputed
         (idx_train, label_train, idx_val, label_val, idx_test, label_test) used in place of get_batch_info."""
         assert train_ratio + val_ratio + test_ratio <= 1.0
-        self._check_model(self.model)
+        _check_node_dist(self._check_model(self.model), node_dist_list)
         model, loss_model, optimizer, classifier = self.prepare(load_model, model_file, classifier_file, lr, weight_decay, train_classifier)
         if batch_info is None:
             batch_info = self.get_batch_info(learning_type, node_labels, edge_labels, edge_list, batch_size, shuffle, train_ratio, val_ratio,

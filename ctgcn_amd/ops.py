@@ -2610,3 +2610,315 @@ def batch_norm_act(x, weight, bias, mean=None, var=None, relu=True, p=0.0, key=0
     mean = None if mean is None else mean.detach().contiguous()
     var = None if var is None else var.detach().contiguous()
     return _BatchNormAct.apply(_row_view(x), weight.contiguous(), bias.contiguous(), mean, var, bool(relu), p, int(key) & (2 ** 64 - 1), float(eps))
+
+
+# ------------------------------------------------------------------------- P-GNN baseline (ctgcn_pgnn.hip)
+PGNN_EPI_NONE, PGNN_EPI_NORM = 0, 1
+PGNN_PULL_PIECE = 512            # (n, a) items per piece of a pull list of the backward (one wave per piece)
+PGNN_TABLE_PIECE = 4096          # items per piece of a table entry's list (one block per piece)
+PGNN_MAX_TABLE = 4096            # distinct values of dists_max above which pgnn_conv takes the composed formulation
+
+
+def _pack_anchor_sets(anchorset_list, device):
+    """(offsets int32 [A + 1], members int32) on the device from a list of 1-D index arrays / tensors"""
+    sets = [s if isinstance(s, torch.Tensor) else torch.as_tensor(s) for s in anchorset_list]
+    if not sets:
+        raise ValueError("no anchor sets")
+    if any(s.dim() != 1 for s in sets):
+        raise ValueError("every anchor set is a 1-D list of node ids")
+    sizes = torch.tensor([0] + [int(s.numel()) for s in sets], dtype=torch.int64)
+    offsets = sizes.cumsum(0).to(torch.int32).to(device)
+    members = torch.cat([s.to(device=device, dtype=torch.int32) for s in sets]) if int(sizes.sum()) else torch.empty(0, dtype=torch.int32, device=device)
+    return offsets, members.contiguous()
+
+
+def pgnn_anchor_dist(adj_or_csr, anchorset_list, cutoff=-1, node_ids=False):
+    """(level, dist_max, pos, node): ctgcn_pgnn_anchor_dist over the pattern of a GcnAdj or a (row_ptr, col) pair of device tensors, for
+    a list of anchor sets (1-D arrays of node ids).  All [n, A]: level int32 (hops to the closest anchor of the set, -1 unreached),
+    dist_max fp32 = 1 / (level + 1) (0 unreached), pos int32 the position inside the set of the closest anchor (the smallest among ties,
+    0 unreached) and, with node_ids, node int32 = that anchor's node id (else None).  cutoff <= 0 is exact, > 0 keeps nodes within that
+    many hops.  The pattern is read as given: an undirected graph is a symmetric pattern."""
+    row_ptr, col = (adj_or_csr.row_ptr, adj_or_csr.col) if hasattr(adj_or_csr, "row_ptr") else adj_or_csr
+    _need_cuda(row_ptr, col)
+    lib = _lib.load()
+    row_ptr, col = _i32(row_ptr), _i32(col)
+    dev = row_ptr.device
+    n, A = row_ptr.numel() - 1, len(anchorset_list)
+    offsets, members = _pack_anchor_sets(anchorset_list, dev)
+    level = torch.empty(n, A, dtype=torch.int32, device=dev)
+    dist = torch.empty(n, A, dtype=torch.float32, device=dev)
+    pos = torch.empty(n, A, dtype=torch.int32, device=dev)
+    node = torch.empty(n, A, dtype=torch.int32, device=dev) if node_ids else None
+    nbytes = int(lib.ctgcn_pgnn_dist_workspace_bytes())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _timed("pgnn_anchor_dist", n=n, A=A, nnz=col.numel()):
+        check(lib.ctgcn_pgnn_anchor_dist(n, col.numel(), ptr(row_ptr), ptr(col), A, ptr(offsets), ptr(members), members.numel(), int(cutoff),
+                                         ptr(level), ptr(dist), ptr(pos), ptr(node), None, ptr(ws), nbytes, _stream()), "ctgcn_pgnn_anchor_dist")
+    return level, dist, pos, node
+
+
+class PgnnPrepared(object):
+    """What the layer kernels read of one anchor draw: lvl int32 [n, A] indexing values fp32 [U] (the distinct entries of dists_max) and
+    idx int32 [n, A]; for the backward, built on first use, the transposed index (the items n A + a sorted by idx, cut into pieces of
+    at most `piece`) and the items sorted by lvl.  composed: more than PGNN_MAX_TABLE distinct values, no table."""
+
+    def __init__(self, dists_max, dists_argmax, n, levels=None, piece=None):
+        _need_cuda(dists_max, dists_argmax)
+        if dists_max.dim() != 2 or tuple(dists_argmax.shape) != tuple(dists_max.shape) or dists_max.shape[0] != n or dists_max.shape[1] < 1:
+            raise ValueError("dists_max and dists_argmax must be [%d, A] with A >= 1, got %s and %s" % (n, tuple(dists_max.shape), tuple(dists_argmax.shape)))
+        self.n, self.A = int(n), int(dists_max.shape[1])
+        if self.n * self.A >= 2 ** 31:
+            raise ValueError("n A = %d reaches 2^31" % (self.n * self.A))
+        self.device = dists_max.device
+        self.piece = int(PGNN_PULL_PIECE if piece is None else piece)
+        if self.piece < 1:
+            raise ValueError("piece must be >= 1")
+        if self.n and (int(dists_argmax.min()) < 0 or int(dists_argmax.max()) >= self.n):
+            raise ValueError("dists_argmax outside [0, %d)" % self.n)
+        self.idx = _i32(dists_argmax)
+        if self.idx is dists_argmax:               # the cache watches the caller's tensor through a weak reference: hold a copy, not the tensor
+            self.idx = self.idx.clone()
+        self.composed = False
+        if levels is not None:                                     # the distance pass's integer levels: entry u is 1 / u, entry 0 unreached
+            self.lvl = (levels.to(torch.int32) + 1).contiguous()
+            U = (int(self.lvl.max()) if self.n else 0) + 1
+            self.values = torch.ones(U, dtype=torch.float32, device=self.device) / torch.arange(U, dtype=torch.float32, device=self.device)
+            self.values[0] = 0.0
+        else:
+            values, inverse = torch.unique(dists_max.to(torch.float32), return_inverse=True)
+            self.values = values
+            self.composed = values.numel() > PGNN_MAX_TABLE
+            self.lvl = None if self.composed else inverse.to(torch.int32).contiguous()
+        self._pull = None
+        self._table = None
+
+    @staticmethod
+    def _pieces(keys, buckets, piece):
+        """keys int32 [items] in [0, buckets): (perm int32 of the items sorted by key, ascending inside a bucket; bucket of each piece;
+        lo; hi; first piece of each bucket [buckets + 1]), pieces of at most `piece` items, none for an empty bucket"""
+        dev = keys.device
+        perm = torch.sort(keys, stable=True).indices.to(torch.int32)
+        count = torch.bincount(keys, minlength=buckets)
+        start = count.cumsum(0) - count
+        np_ = (count + piece - 1) // piece
+        first = torch.zeros(buckets + 1, dtype=torch.int64, device=dev)
+        first[1:] = np_.cumsum(0)
+        bucket = torch.repeat_interleave(torch.arange(buckets, device=dev), np_)
+        k = torch.arange(bucket.numel(), device=dev) - first[bucket]
+        lo = start[bucket] + k * piece
+        hi = torch.minimum(lo + piece, start[bucket] + count[bucket])
+        return perm, bucket, lo, hi, first, np_
+
+    def pull(self):
+        """(perm, pieces int32 [4, n_pieces], multi_node, multi_ptr, part_rows) of ctgcn_pgnn_conv_bwd_pull_f32"""
+        if self._pull is None:
+            perm, node, lo, hi, first, np_ = self._pieces(self.idx.view(-1), self.n, self.piece)
+            multi = (np_ > 1).nonzero().view(-1)
+            multi_ptr = torch.zeros(multi.numel() + 1, dtype=torch.int64, device=self.device)
+            multi_ptr[1:] = np_[multi].cumsum(0)
+            slot = torch.full((self.n,), -1, dtype=torch.int64, device=self.device)
+            slot[multi] = multi_ptr[:-1]
+            k = torch.arange(node.numel(), device=self.device) - first[node]
+            dst = torch.where(slot[node] < 0, node, -1 - (slot[node] + k))
+            pieces = torch.stack((node, lo, hi, dst)).to(torch.int32).contiguous()
+            self._pull = (perm, pieces, multi.to(torch.int32), multi_ptr.to(torch.int32), int(multi_ptr[-1]))
+        return self._pull
+
+    def table_lists(self):
+        """(perm, pieces int32 [2, n_pieces], piece_ptr int32 [U + 1]) of ctgcn_pgnn_table_grad_f32"""
+        if self._table is None:
+            perm, _, lo, hi, first, _ = self._pieces(self.lvl.view(-1), self.values.numel(), PGNN_TABLE_PIECE)
+            self._table = (perm, torch.stack((lo, hi)).to(torch.int32).contiguous(), first.to(torch.int32))
+        return self._table
+
+
+_pgnn_cache = []                 # (weakref dists_max, weakref dists_argmax, versions, n, piece, prepared), the newest last
+_PGNN_CACHE_SIZE = 64
+
+
+def pgnn_prepare(dists_max, dists_argmax, n=None, levels=None, piece=None):
+    """The PgnnPrepared of a (dists_max, dists_argmax) pair, built on first use and cached against the two tensors themselves (their
+    identity and version counters, as the plane cache is keyed on its operands), so every layer and every epoch of one anchor draw
+    shares one.  levels: the distance pass's integer levels, which spare the torch.unique over the floats."""
+    import weakref
+    n = dists_max.shape[0] if n is None else int(n)
+    piece = int(PGNN_PULL_PIECE if piece is None else piece)
+    versions = (dists_max._version, dists_argmax._version)
+    live = []
+    hit = None
+    for entry in _pgnn_cache:
+        a, b = entry[0](), entry[1]()
+        if a is None or b is None:
+            continue
+        live.append(entry)
+        if a is dists_max and b is dists_argmax and entry[2] == versions and entry[3] == n and entry[4] == piece:
+            hit = entry[5]
+    _pgnn_cache[:] = live[-_PGNN_CACHE_SIZE:]
+    if hit is None:
+        hit = PgnnPrepared(dists_max, dists_argmax, n, levels=levels, piece=piece)
+        _pgnn_cache.append((weakref.ref(dists_max), weakref.ref(dists_argmax), versions, n, piece, hit))
+    return hit
+
+
+def _wrap64(v):
+    v &= 2 ** 64 - 1
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+def _mix64(z):
+    """ctgcn_rng.h's splitmix64 finaliser on int64 tensors (two's complement wraps like uint64; shifts are made logical by masks)"""
+    z = z + _wrap64(0x9e3779b97f4a7c15)
+    z = (z ^ ((z >> 30) & (2 ** 34 - 1))) * _wrap64(0xbf58476d1ce4e5b9)
+    z = (z ^ ((z >> 27) & (2 ** 37 - 1))) * _wrap64(0x94d049bb133111eb)
+    return z ^ ((z >> 31) & (2 ** 33 - 1))
+
+
+def dropout_keep_mask(key, n, d, p, device):
+    """bool [n, d]: entry (i, c) is kept iff ctgcn_u01(key, i, c) >= p, the draw of every counter-based dropout epilogue, in torch
+    integer ops (the composed fallback of pgnn_conv; the kernels make the draw themselves)"""
+    rows = torch.arange(n, dtype=torch.int64, device=device)[:, None]
+    cols = torch.arange(d, dtype=torch.int64, device=device)[None, :]
+    a = _mix64(torch.full((1, 1), _wrap64(int(key)), dtype=torch.int64, device=device))
+    x = _mix64(a ^ _mix64(rows * 0x100000001b3 + cols))
+    u = ((x >> 11) & (2 ** 53 - 1)).to(torch.float64) * (1.0 / 9007199254740992.0)
+    return u >= p
+
+
+def pgnn_conv_composed(PS, dists_max, dists_argmax, w_p, b_p, need_pos=True, need_struct=True, epi=PGNN_EPI_NONE, p=0.0, key=0):
+    """pgnn_conv in stock torch ops, materialising [n, A, out]: the route for a dists_max with more than PGNN_MAX_TABLE distinct
+    values (no table to index), and what tools/pgnn_bench.py measures the fused pass against"""
+    d = PS.shape[1] // 2
+    m = torch.relu(dists_max.unsqueeze(-1) * PS[:, :d][dists_argmax.reshape(-1)].view(dists_argmax.shape[0], dists_argmax.shape[1], d)
+                   + PS[:, None, d:])
+    pos = strct = None
+    if need_pos:
+        pos = m.matmul(w_p) if b_p is None else m.matmul(w_p) + b_p
+        if epi == PGNN_EPI_NORM:
+            pos = torch.nn.functional.normalize(pos, p=2, dim=-1)
+    if need_struct:
+        strct = m.mean(dim=1)
+        if p > 0:
+            strct = strct * dropout_keep_mask(key, strct.shape[0], d, p, strct.device).to(strct.dtype) / (1.0 - p)
+    return pos, strct
+
+
+def _pgnn_common(prep, PS, table):
+    n, d = PS.shape[0], PS.shape[1] // 2
+    return (n, prep.A, d, ptr(PS), PS.stride(0), ptr(prep.lvl), ptr(table), table.numel())
+
+
+class _PgnnConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, PS, table, w_p, b_p, prep, need_pos, need_struct, epi, p, key):
+        lib = _lib.load()
+        n, d, A, dev = PS.shape[0], PS.shape[1] // 2, prep.A, PS.device
+        norm_on = need_pos and epi == PGNN_EPI_NORM
+        pos = torch.empty(n, A, dtype=torch.float32, device=dev) if need_pos else None
+        strct = torch.empty(n, d, dtype=torch.float32, device=dev) if need_struct else None
+        xraw = torch.empty(n, A, dtype=torch.float32, device=dev) if norm_on else None
+        with torch.cuda.device(dev), _timed("pgnn_conv_fwd", n=n, A=A, d=d):
+            check(lib.ctgcn_pgnn_conv_fwd_f32(*_pgnn_common(prep, PS, table), ptr(prep.idx), ptr(w_p), ptr(b_p), ptr(pos), ptr(strct), d,
+                                              1 if norm_on else 0, ptr(xraw), p if need_struct else 0.0, key, _stream()), "ctgcn_pgnn_conv_fwd_f32")
+        ctx.prep, ctx.norm_on, ctx.p, ctx.key, ctx.has_b = prep, norm_on, (p if need_struct else 0.0), key, b_p is not None
+        ctx.save_for_backward(PS, table, w_p, *((xraw,) if norm_on else ()))
+        ctx.set_materialize_grads(False)
+        return pos, strct
+
+    @staticmethod
+    def backward(ctx, g_pos, g_struct):
+        if g_pos is None and g_struct is None:
+            return (None,) * 10
+        lib = _lib.load()
+        PS, table, w_p = ctx.saved_tensors[:3]
+        xraw = ctx.saved_tensors[3] if ctx.norm_on else None
+        prep = ctx.prep
+        n, d, A, dev = PS.shape[0], PS.shape[1] // 2, prep.A, PS.device
+        g_pos = None if g_pos is None else g_pos.contiguous()
+        g_struct = None if g_struct is None else _row_view(g_struct)
+        gPS = torch.zeros(n, 2 * d, dtype=torch.float32, device=dev)
+        gd = torch.empty(n, A, dtype=torch.float32, device=dev)
+        normalize = ctx.norm_on and g_pos is not None
+        gx = torch.empty(n, A, dtype=torch.float32, device=dev) if normalize else None
+        gse = torch.empty(n, d, dtype=torch.float32, device=dev) if g_struct is not None else None
+        g_w = torch.empty(d, dtype=torch.float32, device=dev)
+        g_b = torch.empty(1, dtype=torch.float32, device=dev)
+        common = _pgnn_common(prep, PS, table)
+        with torch.cuda.device(dev):
+            nbytes = int(lib.ctgcn_pgnn_bwd_row_workspace_bytes(n, d))
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+            with _timed("pgnn_conv_bwd_row", n=n, A=A, d=d):
+                check(lib.ctgcn_pgnn_conv_bwd_row_f32(*common, ptr(prep.idx), ptr(w_p), ptr(g_pos), ptr(xraw), 1 if normalize else 0,
+                                                      ptr(g_struct), 0 if g_struct is None else g_struct.stride(0), ctx.p, ctx.key, ptr(gPS), 2 * d,
+                                                      ptr(gd), ptr(gx), ptr(gse), d, ptr(g_w), ptr(g_b), ptr(ws), nbytes, _stream()),
+                      "ctgcn_pgnn_conv_bwd_row_f32")
+            del ws
+            if ctx.needs_input_grad[0]:
+                perm, pieces, multi_node, multi_ptr, part_rows = prep.pull()
+                nbytes = int(lib.ctgcn_pgnn_bwd_pull_workspace_bytes(part_rows, d))
+                ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+                with _timed("pgnn_conv_bwd_pull", n=n, A=A, d=d):
+                    check(lib.ctgcn_pgnn_conv_bwd_pull_f32(*common, ptr(w_p), ptr(gx if normalize else g_pos), ptr(gse), d, ptr(perm), ptr(pieces),
+                                                           pieces.shape[1], ptr(multi_node), ptr(multi_ptr), multi_node.numel(), part_rows,
+                                                           ptr(gPS), 2 * d, ptr(ws), nbytes, _stream()), "ctgcn_pgnn_conv_bwd_pull_f32")
+                del ws
+            g_table = None
+            if ctx.needs_input_grad[1]:
+                perm, pieces, piece_ptr = prep.table_lists()
+                g_table = torch.empty(table.numel(), dtype=torch.float32, device=dev)
+                nbytes = int(lib.ctgcn_pgnn_table_grad_workspace_bytes(pieces.shape[1]))
+                ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+                with _timed("pgnn_table_grad", n=n, A=A):
+                    check(lib.ctgcn_pgnn_table_grad_f32(n * A, table.numel(), ptr(gd), ptr(perm), ptr(pieces), pieces.shape[1], ptr(piece_ptr),
+                                                        ptr(g_table), ptr(ws), nbytes, _stream()), "ctgcn_pgnn_table_grad_f32")
+        have_pos = g_pos is not None
+        return (gPS if ctx.needs_input_grad[0] else None, g_table, g_w if (have_pos and ctx.needs_input_grad[2]) else None,
+                g_b if (have_pos and ctx.has_b and ctx.needs_input_grad[3]) else None, None, None, None, None, None, None)
+
+
+def pgnn_conv(PS, dists_max, dists_argmax, w_p, b_p=None, table=None, need_pos=True, need_struct=True, epi=PGNN_EPI_NONE, p=0.0, key=0,
+              piece=None):
+    """(pos [n, A] or None, struct [n, out] or None) of one P-GNN layer after its product PS [n, 2 out] = P | S:
+    m = relu(d'[i, a] P[dists_argmax[i, a]] + S[i]), pos = <m, w_p> + b_p, struct = mean_a m, with m formed in registers: nothing of
+    n x A x out exists, in the forward or the backward.  d' = table[k] where dists_max[i, a] == pgnn_prepare(dists_max, dists_argmax).values[k]:
+    build a table from that tensor, entry for entry, and from nothing else.  Its order is whatever the prepared index has: ascending
+    for a pair that went through torch.unique, but 0, 1, 1/2, 1/3, ... (entry 0 present even when nothing is unreached) for a pair that
+    baseline.pgnn.get_dist_max made from a DistHandle.  So a trainable distance transform runs under autograd on those few values and
+    the kernel indexes its result; table None: d' = dists_max.  epi PGNN_EPI_NORM: F.normalize(pos, p=2, dim=-1).  p > 0: dropout on struct,
+    entry (i, c) kept iff u01(key, i, c) >= p.  Differentiable in PS, table, w_p and b_p; an output that was not asked for costs nothing
+    and sends no gradient (w_p and b_p get None without pos).  The prepared index is cached against the two dists tensors
+    (pgnn_prepare).  More than PGNN_MAX_TABLE distinct values in dists_max: the composed torch formulation (table must then be None)."""
+    _need_cuda(PS, dists_max, dists_argmax, w_p, b_p, table)
+    if not (need_pos or need_struct):
+        raise ValueError("neither pos nor struct asked for")
+    if epi not in (PGNN_EPI_NONE, PGNN_EPI_NORM):
+        raise ValueError("epi must be PGNN_EPI_NONE or PGNN_EPI_NORM")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p must lie in [0, 1), got %r" % p)
+    if PS.dim() != 2 or PS.shape[1] < 2 or PS.shape[1] % 2:
+        raise ValueError("PS must be [n, 2 out], got %s" % (tuple(PS.shape),))
+    n, d = PS.shape[0], PS.shape[1] // 2
+    if not 1 <= d <= 512:
+        raise ValueError("out = %d outside [1, 512]" % d)
+    w_p = w_p.reshape(-1)
+    if w_p.numel() != d or (b_p is not None and b_p.numel() != 1):
+        raise ValueError("w_p must have %d entries and b_p one" % d)
+    if any(t is not None and t.dtype != torch.float32 for t in (PS, w_p, b_p, table)):
+        raise TypeError("fp32 features and weights expected")
+    if any(t is not None and t.device != PS.device for t in (dists_max, dists_argmax, w_p, b_p, table)):
+        raise ValueError("every operand must be on one device")
+    key = int(key) & (2 ** 64 - 1)
+    prep = pgnn_prepare(dists_max, dists_argmax, n, piece=piece)
+    if prep.composed:
+        if table is not None:
+            raise ValueError("dists_max has %d distinct values, above PGNN_MAX_TABLE = %d: no table" % (prep.values.numel(), PGNN_MAX_TABLE))
+        return pgnn_conv_composed(PS, dists_max.to(torch.float32), dists_argmax.to(torch.int64), w_p, b_p, need_pos, need_struct, epi, p, key)
+    if table is None:
+        table = prep.values
+    table = table.reshape(-1)
+    if table.numel() != prep.values.numel():
+        raise ValueError("table must have %d entries (the distinct values of dists_max)" % prep.values.numel())
+    if n == 0:
+        return (PS.new_zeros(0, prep.A) if need_pos else None), (PS.new_zeros(0, d) if need_struct else None)
+    return _PgnnConv.apply(_row_view(PS), table.contiguous(), w_p.contiguous(), None if b_p is None else b_p.reshape(-1).contiguous(), prep,
+                           bool(need_pos), bool(need_struct), int(epi), p, key)

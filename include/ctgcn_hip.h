@@ -1020,6 +1020,66 @@ int ctgcn_bn_bwd_f32(int64_t n, int32_t d, const float *x, int64_t ldx, const fl
                      const float *weight, const float *bias, int32_t relu, double p, uint64_t key, int32_t batch_stats, float *dx,
                      int64_t lddx, float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The P-GNN baseline (reference baseline/pgnn.py; ctgcn_amd/baseline/pgnn.py), ctgcn_pgnn.hip.
+ *
+ * ctgcn_pgnn_anchor_dist: for n_sets anchor sets, packed as offsets [n_sets + 1] (ascending from 0 to n_members) and members
+ *   [n_members] (node ids, a set may list a node twice), a multi-source BFS per set over the pattern of the CSR (values are not read;
+ *   self-loops, repeated entries and column indices outside [0, n) are harmless; the pattern is taken as given, so an undirected graph
+ *   is a symmetric pattern).  cutoff <= 0: exact; > 0: nodes within that many hops.  Outputs, each [n, n_sets] with the set index
+ *   fastest: level (hops to the closest anchor of the set, -1 unreached; int32, so no distance wraps), dist_max = 1 / (level + 1) as
+ *   fp32 division (0 unreached), pos = the position inside the set of the closest anchor, the smallest among equally close ones (0
+ *   unreached): the reference's np.max / np.argmax over its dense matrix; node_id, when not null, members[offsets[s] + pos] (0 for an
+ *   empty set).  levels_run (host, may be null) receives the number of passes.  The only atomic is an integer minimum while seeding;
+ *   results do not depend on the order of execution.  workspace: ctgcn_pgnn_dist_workspace_bytes() bytes.  Reads a flag back after every pass:
+ *   synchronises `stream`.  CTGCN_E_INVALID for bad sizes, null pointers, offsets that do not ascend from 0 to n_members or a member
+ *   outside [0, n); CTGCN_E_UNSUPPORTED when n · n_sets reaches 2^31.
+ *
+ * ctgcn_pgnn_conv_fwd_f32: PS [n, 2 d] = P | S (row stride ldps), lvl and idx int32 [n, n_sets] (entries are clamped into
+ *   [0, n_table) and [0, n)), table [n_table], w_p [d], b_p [1] or null.  m = relu(table[lvl[i, a]] · P[idx[i, a]] + S[i]);
+ *   pos[i, a] = ⟨m, w_p⟩ + b_p and strct[i] = mean_a m; each is computed when its pointer is not null, at least one.  normalize 1:
+ *   pos rows are divided by max(‖row‖₂, 1e-12) and xraw [n, n_sets] receives pos before that, which the backward reads.  p > 0: entry (i, c) of strct is kept iff
+ *   u01(key, i, c) >= p and scaled by 1 / (1 − p).  1 <= d <= 512, n_sets >= 1.
+ * ctgcn_pgnn_conv_bwd_row_f32: per node, with everything per (i, a, c) made again, gm = (gx[i, a] · w_p + gs[i] / n_sets) ⊙ [m > 0]
+ *   where gx is g_pos taken back through the normalisation (in fp64, from xraw) when normalize, and gs is
+ *   g_struct through the dropout draw made again; g_pos or g_struct may be null (that output was not asked for).  Writes
+ *   gPS[i, d:] = Σ_a gm, gd[i, a] = ⟨gm, P[idx]⟩, gx [n, n_sets] when normalize, gse [n, d] = gs / n_sets when g_struct is given, and
+ *   g_w [d] = Σ m · gx, g_b [1] = Σ gx as per-block partial sums (ctgcn_pgnn_bwd_row_workspace_bytes(n, d) bytes) added in block order.
+ * ctgcn_pgnn_conv_bwd_pull_f32: gPS[j, :d] = Σ_{(i, a): idx = j} d' · gm over the transposed index: perm [n · n_sets] the items
+ *   i · n_sets + a sorted by idx (ascending inside a node's list), pieces int32 [4][n_pieces] = node, lo, hi (a range of perm) and dst
+ *   (>= 0: the piece is the node's whole list and is written to that row of gPS; < 0: to row −1 − dst of the workspace; a row at or beyond part_rows is not written), multi_node
+ *   [n_multi] / multi_ptr [n_multi + 1]: the nodes with several pieces and their workspace rows, added in order.  gx is g_pos itself
+ *   without normalisation, or null; gse as written by the row pass, or null.  Rows of gPS[:, :d] of nodes nobody chose are not
+ *   written.  workspace: ctgcn_pgnn_bwd_pull_workspace_bytes(part_rows, d).
+ * ctgcn_pgnn_table_grad_f32: g_table[u] = Σ_{lvl = u} gd over perm (the items sorted by lvl), pieces int32 [2][n_pieces] = lo, hi,
+ *   piece_ptr [n_table + 1] the pieces of each entry; a block sums a piece in a fixed order, the pieces are added in order.
+ * Returns CTGCN_E_INVALID for null pointers and bad sizes, CTGCN_E_UNSUPPORTED for d > 512 or n · n_sets >= 2^31,
+ * CTGCN_E_WORKSPACE for a workspace that is too small; 0 for n = 0.  No float atomics; repeated calls are bit-identical.
+ * The sums over anchor sets, nodes, list items and blocks are kept in fp64; what is written is fp32.
+ */
+size_t ctgcn_pgnn_dist_workspace_bytes(void);
+int ctgcn_pgnn_anchor_dist(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *col, int32_t n_sets, const int32_t *offsets,
+                           const int32_t *members, int32_t n_members, int32_t cutoff, int32_t *level, float *dist_max, int32_t *pos,
+                           int32_t *node_id, int32_t *levels_run, void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_pgnn_conv_fwd_f32(int64_t n, int32_t n_sets, int32_t d, const float *PS, int64_t ldps, const int32_t *lvl, const float *table,
+                            int32_t n_table, const int32_t *idx, const float *w_p, const float *b_p, float *pos, float *strct,
+                            int64_t ldstruct, int32_t normalize, float *xraw, double p, uint64_t key, void *stream);
+size_t ctgcn_pgnn_bwd_row_workspace_bytes(int64_t n, int32_t d);
+int ctgcn_pgnn_conv_bwd_row_f32(int64_t n, int32_t n_sets, int32_t d, const float *PS, int64_t ldps, const int32_t *lvl, const float *table,
+                                int32_t n_table, const int32_t *idx, const float *w_p, const float *g_pos, const float *xraw,
+                                int32_t normalize, const float *g_struct, int64_t ldgs, double p, uint64_t key,
+                                float *gPS, int64_t ldg, float *gd, float *gx, float *gse, int64_t ldgse, float *g_w, float *g_b,
+                                void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_pgnn_bwd_pull_workspace_bytes(int64_t part_rows, int32_t d);
+int ctgcn_pgnn_conv_bwd_pull_f32(int64_t n, int32_t n_sets, int32_t d, const float *PS, int64_t ldps, const int32_t *lvl, const float *table,
+                                 int32_t n_table, const float *w_p, const float *gx, const float *gse, int64_t ldgse, const int32_t *perm,
+                                 const int32_t *pieces, int64_t n_pieces, const int32_t *multi_node, const int32_t *multi_ptr,
+                                 int64_t n_multi, int64_t part_rows, float *gPS, int64_t ldg, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+size_t ctgcn_pgnn_table_grad_workspace_bytes(int64_t n_pieces);
+int ctgcn_pgnn_table_grad_f32(int64_t items, int32_t n_table, const float *gd, const int32_t *perm, const int32_t *pieces, int64_t n_pieces,
+                              const int32_t *piece_ptr, float *g_table, void *workspace, size_t workspace_bytes, void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
