@@ -146,3 +146,78 @@ def power_law(n, m, seed, hub_frac=0.25):
     hub = rng.choice(np.arange(1, n - 8), int(n * hub_frac), replace=False)
     edges += [(0, int(h)) for h in hub]
     return csr(n, edges)
+
+
+LAYER_SIZES = (1, 4, 5, 8, 9, 16, 17, 32, 33, 64, 65, 300)
+
+
+def layered(sizes=LAYER_SIZES, isolated=0, p=0.5, seed=0):
+    """(n, (indptr, indices), levels): vertices numbered layer by layer from vertex 0 (sizes[0] must be 1), edges between
+    consecutive layers only: every vertex gets one random parent in the layer before it, and every other pair of consecutive layers
+    is joined with probability p.  So the BFS levels from vertex 0 are the layers (levels[v] = layer of v; -1 for the `isolated`
+    vertices appended at the end) and row lengths run from 1 to most of two layers."""
+    rng = np.random.default_rng(seed)
+    assert sizes[0] == 1
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    edges = []
+    for k in range(1, len(sizes)):
+        prev = np.arange(starts[k - 1], starts[k])
+        for v in range(starts[k], starts[k + 1]):
+            edges.append((int(rng.choice(prev)), v))
+            edges += [(int(u), v) for u in prev[rng.random(len(prev)) < p]]
+    n = int(starts[-1]) + isolated
+    levels = np.full(n, -1, np.int64)
+    for k in range(len(sizes)):
+        levels[starts[k]:starts[k + 1]] = k
+    return n, csr(n, edges), levels
+
+
+# ------------------------------------------------------------------------------------------------ ridge passes in long double
+U = 2.0 ** -53       # unit roundoff of float64
+
+
+def gamma(k):
+    """Higham's γ_k = k u / (1 - k u): the relative error bound of k chained float64 roundings."""
+    return k * U / (1.0 - k * U)
+
+
+def fold_grams(X, Y, k):
+    """Per fold f of the unshuffled k-fold split: (Z_fᵀ Z_f restricted to [d+1, d+1+T], |Z_f|ᵀ|Z_f| likewise, rows of f), with
+    Z = [X 1 Y], in np.longdouble."""
+    X = np.asarray(X).astype(np.longdouble)
+    Y = np.asarray(Y).astype(np.longdouble).reshape(len(X), -1)
+    n, d = X.shape
+    Z = np.hstack([X, np.ones((n, 1), np.longdouble), Y])
+    b = kfold_bounds(n, k)
+    out = []
+    for f in range(k):
+        Zf = Z[b[f]:b[f + 1]]
+        out.append((Zf[:, :d + 1].T @ Zf, np.abs(Zf[:, :d + 1]).T @ np.abs(Zf), int(b[f + 1] - b[f])))
+    return out
+
+
+def fold_sse(X, Y, W, target_of, k, chain):
+    """(sse, bound), each [k, P]: sse[f, p] = Σ_{rows r of fold f} (Y[r, target_of[p]] - (X[r]·W[f, p, :d] + W[f, p, d]))² in
+    np.longdouble, and the running-error bound of a float64 evaluation that forms the dot in any order, adds the intercept,
+    subtracts from y, squares, and sums the squares with every term passing through at most `chain` additions (u = 2^-53):
+        e_dot = γ_d Σ_j |x_j w_j|;  e_pred = e_dot + u |pred|;  e_res = e_pred + u |res|;
+        bound = Σ_r (2 |res| e_res + e_res²) + γ_chain Σ_r (|res| + e_res)²."""
+    X = np.asarray(X).astype(np.longdouble)
+    Y = np.asarray(Y).astype(np.longdouble).reshape(len(X), -1)
+    W = np.asarray(W).astype(np.longdouble)
+    n, d = X.shape
+    b = kfold_bounds(n, k)
+    P = W.shape[1]
+    sse, bound = np.zeros((k, P), np.longdouble), np.zeros((k, P), np.longdouble)
+    for f in range(k):
+        Xf, Yf = X[b[f]:b[f + 1]], Y[b[f]:b[f + 1]]
+        w, c = W[f, :, :d], W[f, :, d]
+        dot = Xf @ w.T                                              # [rows, P]
+        pred = dot + c[None, :]
+        res = Yf[:, np.asarray(target_of)] - pred
+        e_dot = gamma(d) * (np.abs(Xf) @ np.abs(w).T)
+        e_pred = e_dot + U * np.abs(pred)
+        e_res = e_pred + U * np.abs(res)
+        sse[f] = (res ** 2).sum(0)
+        bound[f] = (2 * np.abs(res) * e_res + e_res ** 2).sum(0) + gamma(chain) * ((np.abs(res) + e_res) ** 2).sum(0)
+    return sse, bound

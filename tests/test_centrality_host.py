@@ -220,3 +220,61 @@ def test_cpu_tensors_fail_loudly():
         CP.centralities(rp, col)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         CP.ridge_cv_errors(torch.zeros(10, 4), torch.ones(10, 4), [1.0])
+
+
+# ------------------------------------------------------------------------------------------------ mirrors used by test_gpu_cent_shapes.py
+def test_layered_graph_has_the_stated_levels():
+    n, (indptr, indices), levels = R.layered(isolated=6)
+    assert n == sum(R.LAYER_SIZES) + 6
+    A = R.adjacency(indptr, indices, n)
+    assert (A != A.T).nnz == 0 and A.diagonal().sum() == 0
+    dist = np.full(n, -1)
+    dist[0], front, k = 0, np.array([0]), 0
+    while len(front):                                              # a plain BFS, apart from R.brandes
+        k += 1
+        nxt = np.unique(np.concatenate([indices[indptr[v]:indptr[v + 1]] for v in front]))
+        front = nxt[dist[nxt] < 0]
+        dist[front] = k
+    assert np.array_equal(dist, levels)
+    assert [int((dist == k).sum()) for k in range(len(R.LAYER_SIZES))] == list(R.LAYER_SIZES)
+    deg = np.diff(indptr)
+    assert np.all(deg[levels >= 0] > 0) and not deg[levels < 0].any()
+    # rows shorter and longer than 16 lanes where a level gets 16 lanes per vertex, and a row of more than 64 for a single source
+    assert deg[levels == 5].min() < 16 < deg[levels == 5].max() and deg[levels == 10].min() > 64
+    bc, r, D = R.brandes(indptr, indices, n, sources=[0, n - 1])
+    assert r.tolist() == [n - 6, 1] and D.tolist() == [int((np.arange(len(R.LAYER_SIZES)) * R.LAYER_SIZES).sum()), 0]
+
+
+def test_star_closed_form_is_the_references():
+    """What test_gpu_cent_shapes.py asserts at 120 001 vertices, on a star small enough for R.brandes: from the hub every leaf is at
+    distance 1 and nothing lies between; from a leaf the hub is at 1 and the other n - 2 leaves at 2, each reached through the hub
+    alone, so the hub's dependency is n - 2."""
+    n, k = 50, 7
+    bc, r, D = R.brandes(*R.star(n), n, sources=np.arange(k))
+    want = np.zeros(n)
+    want[0] = (k - 1) * (n - 2)
+    assert np.array_equal(bc, want) and np.array_equal(r, np.full(k, n))
+    assert np.array_equal(D, [n - 1] + [1 + 2 * (n - 2)] * (k - 1))
+
+
+def test_long_double_ridge_mirrors():
+    rng = np.random.default_rng(5)
+    n, d, T, F, P = 37, 6, 3, 4, 5
+    X, Y = rng.standard_normal((n, d)), rng.random((n, T))
+    Z = np.hstack([X, np.ones((n, 1)), Y])
+    b = R.kfold_bounds(n, F)
+    for f, (g, absg, rows) in enumerate(R.fold_grams(X, Y, F)):
+        Zf = Z[b[f]:b[f + 1]]
+        assert rows == len(Zf) and g.dtype == np.longdouble and g.shape == (d + 1, d + 1 + T)
+        assert np.all(np.abs(Zf[:, :d + 1].T @ Zf - g) <= rows * 2.0 ** -52 * absg)
+        assert g[d, d] == rows
+    W = rng.standard_normal((F, P, d + 1))
+    tgt = [2, 0, 0, 1, 2]
+    sse, bound = R.fold_sse(X, Y, W, tgt, F, chain=n)
+    for f in range(F):
+        Xf, Yf = X[b[f]:b[f + 1]], Y[b[f]:b[f + 1]]
+        for p in range(P):
+            plain = ((Yf[:, tgt[p]] - (Xf @ W[f, p, :d] + W[f, p, d])) ** 2).sum()
+            assert abs(plain - sse[f, p]) <= bound[f, p] <= 1e-13 * sse[f, p]
+            short = ((Yf[1:, tgt[p]] - (Xf[1:] @ W[f, p, :d] + W[f, p, d])) ** 2).sum()      # one row dropped: far outside the bound
+            assert abs(short - sse[f, p]) > 1e6 * bound[f, p]

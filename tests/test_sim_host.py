@@ -132,3 +132,68 @@ def test_file_layer(tmp_path, monkeypatch):
         pred.similarity_prediction_all_time("M")
     with pytest.raises(AssertionError):
         SIM.DataGenerator(base, "1.format", "similarity_data", "nodes_set/nodes.csv", alpha=1.5)
+
+
+# ------------------------------------------------------------------------------------------------ mirrors used by test_gpu_sim_shapes.py
+NP_SUM_SIZES = [2, 7, 8, 9, 127, 128, 129, 136, 137, 4097, 8191, 8192, 8193, 16385, 2049 * 2049]
+
+
+@pytest.mark.parametrize("N", NP_SUM_SIZES)
+def test_np_sum_model_is_numpys_sum(N):
+    """The Python model of numpy's float64 sum (chunks of 8192, pairwise down to blocks of 128 with 8 running sums) gives np.sum's
+    bits at every boundary of that tree, for a 1-D array and for a square 2-D one.  The kernel is held to numpy directly; this test
+    says whether a disagreement there comes from a numpy that sums in another order."""
+    side = int(round(N ** 0.5))
+    for draw in range(4 if N < 100_000 else 1):
+        x = np.random.default_rng(1000 * draw + N).uniform(0.0, 1.0, N)
+        want = _sim_ref.np_sum_model(x)
+        assert want == x.sum() == np.sum(x)
+        if side * side == N:
+            assert want == x.reshape(side, side).sum()
+        assert _sim_ref.normalize(x)[1][2] == _sim_ref.np_sum_model((x - x.min()) / (x.max() - x.min()))
+
+
+def test_np_sum_model_depends_on_the_order():
+    """The sizes above can tell the orders apart: a plain running sum, and a pairwise sum that is not cut into chunks of 8192,
+    differ from numpy's on the same data."""
+    x = np.random.default_rng(3).uniform(0.0, 1.0, 16385)
+    running = 0.0
+    for v in x.tolist():
+        running = running + v
+    assert running != x.sum()
+    assert _sim_ref._np_pairwise(x.tolist()) != x.sum()
+
+
+@pytest.mark.parametrize("pad_zero", [0, 1])
+def test_finish_mirror_is_the_scipy_statement(pad_zero):
+    """finish() on the block of the non-isolated vertices, with 0 joined to the extremes when isolated vertices exist, is the n x n
+    statement of similarity()."""
+    rng = np.random.default_rng(11)
+    m, n = 9, 9 + 3 * pad_zero
+    src, dst = np.triu_indices(m, 1)
+    pick = rng.random(len(src)) < 0.4
+    pick[:m - 1] = True                                           # vertex 0 is joined to all: no isolated vertex inside the block
+    A = _sim_ref.adjacency(src[pick], dst[pick], rng.uniform(0.5, 2.0, pick.sum()), n)
+    lam = SIM.host_lambda_1(A)
+    want = _sim_ref.similarity(A, lam, 0.5, 7).toarray()
+    S = np.zeros((n, n))
+    for _ in range(7):
+        S = (0.5 / lam) * A.dot(S) + np.eye(n)
+    got, (mn, mx), nnz = _sim_ref.finish(S[:m, :m], pad_zero, 1e-6)
+    assert np.array_equal(got, want[:m, :m]) and not want[m:].any() and not want[:, m:].any()
+    assert np.array_equal(nnz, np.count_nonzero(want[:m, :m], axis=1))
+
+
+def test_spearman_sums_mirror_matches_scipy():
+    import scipy.stats
+    rng = np.random.default_rng(2)
+    for N in (2, 3, 257, 4097):
+        x = rng.permutation(N).astype(np.float64)
+        y = rng.integers(0, 5, N).astype(np.float64)
+        y[0], y[-1] = -1.0, 9.0
+        sxy, sxx, syy = _sim_ref.spearman_sums(x, y)
+        rx, ry = scipy.stats.rankdata(x), scipy.stats.rankdata(y)
+        mu = (N + 1) / 2
+        assert (sxy, sxx, syy) == (((rx - mu) * (ry - mu)).sum(), ((rx - mu) ** 2).sum(), ((ry - mu) ** 2).sum())
+        assert abs(sxy / np.sqrt(sxx * syy) - scipy.stats.spearmanr(x, y)[0]) <= 1e-14
+    assert _sim_ref.spearman_sums(np.full(5, 0.3), np.arange(5.0))[1] == 0.0
