@@ -7,19 +7,15 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(_HERE, "csrc", f) for f in ("ctgcn_hip.hip", "ctgcn_gemm.hip", "ctgcn_gru_bwd.hip", "ctgcn_ingest.hip", "ctgcn_walks.hip", "ctgcn_epoch.hip", "ctgcn_eval.hip", "ctgcn_cent.hip", "ctgcn_nodecls.hip", "ctgcn_sim.hip", "ctgcn_supervised.hip", "ctgcn_gcn.hip", "ctgcn_gat.hip", "ctgcn_pool.hip", "ctgcn_pgnn.hip", "ctgcn_export.cpp")]
 HDR = os.path.join(os.path.dirname(_HERE), "include", "ctgcn_hip.h")
-JITTER_HDR = os.path.join(_HERE, "csrc", "ctgcn_jitter.h")     # included by the kernel files (inert without -DCTGCN_JITTER): part of the source hash
-TABLE_HDR = os.path.join(_HERE, "csrc", "ctgcn_table.h")       # descriptor-table upload of the grouped launches (both kernel files)
-RNG_HDR = os.path.join(_HERE, "csrc", "ctgcn_rng.h")           # counter-based RNG of the walk / sampling draws (ctgcn_walks.hip, ctgcn_epoch.hip, ctgcn_eval.hip) and of the dropout draws
-TRY_HDR = os.path.join(_HERE, "csrc", "ctgcn_try.h")           # error macro and LDS opt-in of every kernel file
-LOGREG_HDR = os.path.join(_HERE, "csrc", "ctgcn_logreg.h")     # sigmoid / softplus and the Hessian block pieces (ctgcn_eval.hip, ctgcn_nodecls.hip, ctgcn_epoch.hip, ctgcn_supervised.hip)
-REDUCE_HDR = os.path.join(_HERE, "csrc", "ctgcn_reduce.h")     # fp64 block sum (ctgcn_cent.hip, ctgcn_sim.hip)
 OUT = os.path.join(_HERE, "csrc", "libctgcn_hip.so")
 STAMP = OUT + ".srchash"          # sha256 of the sources + header + this recipe the .so was built from (travels with it, git-ignored)
 
 
 def source_hash():
     h = hashlib.sha256()
-    for f in SRCS + [HDR, JITTER_HDR, TABLE_HDR, RNG_HDR, TRY_HDR, LOGREG_HDR, REDUCE_HDR, os.path.abspath(__file__)]:
+    csrc = os.path.join(_HERE, "csrc")
+    private_hdrs = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))    # every header the kernel files share
+    for f in SRCS + [HDR] + private_hdrs + [os.path.abspath(__file__)]:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:
             h.update(fh.read())

@@ -6,7 +6,7 @@
 // m_i = max_j l_ij comes from a scalar pre-pass: -leakyrelu is decreasing, so m_i = -leakyrelu(u_i + min_j v_j).  With m known before
 // the gather no accumulator is ever rescaled and the pieces of a long row add up like any other sum.
 //
-// Every gather (forward, and the backward's pass over the CSR and over its transpose) is the pull form of ctgcn_gcn.hip with the
+// Every gather (forward, and the backward's pass over the CSR and over its transpose) is the pull form of ctgcn_gather.h with the
 // entry's weight computed on the fly: LPR lanes own a destination row and a float4 (or a float) per lane of it, entries are read LPR
 // at a time and handed round by shuffles, U gathered rows in flight, rows longer than long_threshold go to piece blocks and a
 // finishing kernel.  A lane works for the head its columns lie in; F % 4 == 0 on the float4 path, so a float4 never straddles heads.
@@ -24,31 +24,17 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <initializer_list>
 
+#include "ctgcn_gather.h"
 #include "ctgcn_rng.h"
 #include "ctgcn_try.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int PIECE_FACTOR = 4;        // entries of a long row's piece, in units of long_threshold (as in ctgcn_gcn.hip: GcnAdj.pieces)
-constexpr int PIECE_THREADS = 256;
-constexpr int PIECE_LANES = 32;
-constexpr int PIECE_GROUPS = PIECE_THREADS / PIECE_LANES;
 constexpr int U = 4;                   // gathered rows in flight per lane group
 constexpr int FWD = 0, ROW = 1, COL = 2;
 constexpr int EPI_NONE = 0, EPI_ELU = 1, EPI_ELU_DROP = 2;
 constexpr int MIN_LANES = 16;          // lanes per row of the row-maximum pre-pass
-
-template <int VEC> struct vec_of;
-template <> struct vec_of<4> { using type = f4; };
-template <> struct vec_of<1> { using type = float; };
-
-__device__ __forceinline__ f4 vfma(float a, f4 x, f4 acc) { return f4{fmaf(a, x.x, acc.x), fmaf(a, x.y, acc.y), fmaf(a, x.z, acc.z), fmaf(a, x.w, acc.w)}; }
-__device__ __forceinline__ float vfma(float a, float x, float acc) { return fmaf(a, x, acc); }
 
 struct GatArgs {
     int64_t n;
@@ -83,13 +69,6 @@ struct GatArgs {
     int32_t piece_ld;       // floats per piece: [part_ld] first sum, [part_ld] second sum, [heads rounded up to 4] scalar sums
     float *part;            // [n_long][max_pieces][piece_ld]
 };
-
-__host__ __device__ __forceinline__ int pieces_of(int len, int long_thresh, int max_pieces)
-{
-    const int64_t piece = (int64_t)PIECE_FACTOR * long_thresh;
-    const int64_t np = (len + piece - 1) / piece;
-    return (int)(np < 1 ? 1 : (np > max_pieces ? max_pieces : np));
-}
 
 // what a lane keeps of its own row for the head it works on
 struct Own {
@@ -494,29 +473,6 @@ __global__ __launch_bounds__(DS_COLS * DS_SEGS) void gat_da_sum_kernel(int64_t b
     }
 }
 
-int fail(int code, const char *what, const char *text)
-{
-    char buf[192];
-    snprintf(buf, sizeof(buf), "%s: %s", what, text);
-    return ctgcn_set_error_(code, buf);
-}
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-struct Operand {
-    const void *p;
-    int64_t ld;
-};
-
-// float4 lanes: F (so d too) and every leading dimension a multiple of 4, every base 16-byte aligned
-bool float4_rows(int32_t F, std::initializer_list<Operand> operands)
-{
-    if (F % 4) return false;
-    for (const Operand &o : operands)
-        if (o.p && (o.ld % 4 || !aligned16(o.p))) return false;
-    return true;
-}
-
 template <int KIND>
 int launch_pairs(PairArgs a, int64_t n, hipStream_t st)
 {
@@ -524,7 +480,7 @@ int launch_pairs(PairArgs a, int64_t n, hipStream_t st)
     a.wshift = 0;
     while ((1 << a.wshift) < a.F && a.wshift < 6) ++a.wshift;
     const int64_t blocks = ((a.pairs << a.wshift) + 255) / 256;
-    if (blocks > INT32_MAX) return fail(CTGCN_E_UNSUPPORTED, "gat", "n * heads too large for one launch");
+    if (blocks > INT32_MAX) return ctgcn_fail(CTGCN_E_UNSUPPORTED, "gat", "n * heads too large for one launch");
     hipLaunchKernelGGL(gat_pair_kernel<KIND>, dim3((unsigned)blocks), dim3(256), 0, st, a);
     CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;
@@ -534,23 +490,10 @@ template <int VEC, int MODE>
 int launch(GatArgs a, hipStream_t st)
 {
     a.chunks = (a.d + VEC - 1) / VEC;
-    const int lpr = a.chunks <= 4 ? 4 : a.chunks <= 8 ? 8 : a.chunks <= 16 ? 16 : a.chunks <= 32 ? 32 : 64;
-    const dim3 grid((unsigned)((a.n + 256 / lpr - 1) / (256 / lpr)));
-    switch (lpr) {
-    case 4: hipLaunchKernelGGL((gat_row_kernel<VEC, 4, MODE>), grid, dim3(256), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((gat_row_kernel<VEC, 8, MODE>), grid, dim3(256), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((gat_row_kernel<VEC, 16, MODE>), grid, dim3(256), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((gat_row_kernel<VEC, 32, MODE>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((gat_row_kernel<VEC, 64, MODE>), grid, dim3(256), 0, st, a); break;
-    }
-    CTGCN_TRY(hipGetLastError());
-    if (a.n_long > 0) {
-        hipLaunchKernelGGL((gat_piece_kernel<VEC, MODE>), dim3((unsigned)a.max_pieces, (unsigned)a.n_long), dim3(PIECE_THREADS), 0, st, a);
-        CTGCN_TRY(hipGetLastError());
-        hipLaunchKernelGGL(gat_final_kernel<MODE>, dim3((unsigned)a.n_long), dim3(64), 0, st, a);
-        CTGCN_TRY(hipGetLastError());
-    }
-    return CTGCN_OK;
+    return launch_rows(
+        a, [&](auto lpr, dim3 grid) { hipLaunchKernelGGL((gat_row_kernel<VEC, decltype(lpr)::value, MODE>), grid, dim3(256), 0, st, a); },
+        [&](dim3 grid) { hipLaunchKernelGGL((gat_piece_kernel<VEC, MODE>), grid, dim3(PIECE_THREADS), 0, st, a); },
+        [&](dim3 grid) { hipLaunchKernelGGL(gat_final_kernel<MODE>, grid, dim3(64), 0, st, a); });
 }
 
 template <int MODE>
@@ -564,44 +507,31 @@ int32_t piece_floats(int32_t d, int32_t heads) { return 2 * ((d + 3) & ~3) + ((h
 // the checks every entry point shares; 1 when n == 0 (nothing to do), a negative code on an error
 int check_shape(const char *what, int64_t n, int32_t d, int32_t heads)
 {
-    if (n < 0 || n > INT32_MAX || d < 1 || heads < 1 || d % heads) return fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31, d >= 1, heads >= 1 and d a multiple of heads");
+    if (n < 0 || n > INT32_MAX || d < 1 || heads < 1 || d % heads) return ctgcn_fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31, d >= 1, heads >= 1 and d a multiple of heads");
     return n == 0 ? 1 : 0;
 }
-
-bool bad_p(double p) { return !(p >= 0.0 && p < 1.0); }
 
 // the CSR, attention-dropout and long-row fields of a gather
 int set_gather(GatArgs &a, const char *what, int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, double alpha,
                double p_att, uint64_t key, const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace,
                size_t workspace_bytes)
 {
-    if (!row_ptr || !col) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (n_long < 0 || n_long > n) return fail(CTGCN_E_INVALID, what, "n_long outside [0, n]");
+    if (!row_ptr || !col) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (n_long < 0 || n_long > n) return ctgcn_fail(CTGCN_E_INVALID, what, "n_long outside [0, n]");
     a.n = n; a.d = d; a.heads = heads; a.F = d / heads; a.row_ptr = row_ptr; a.col = col;
     a.alpha = (float)alpha; a.drop = p_att > 0.0; a.p_att = p_att; a.att_scale = 1.0f / (1.0f - (float)p_att); a.key = key;
-    a.long_rows = long_rows; a.n_long = n_long; a.long_thresh = long_threshold;
     a.part_ld = (d + 3) & ~3;
     a.piece_ld = piece_floats(d, heads);
-    if (n_long > 0) {
-        if (!long_rows) return fail(CTGCN_E_INVALID, what, "n_long > 0 without long_rows");
-        if (long_threshold < 1 || long_threshold > INT32_MAX / PIECE_FACTOR) return fail(CTGCN_E_INVALID, what, "long_threshold outside [1, 2^29)");
-        if (n_long > 65535) return fail(CTGCN_E_UNSUPPORTED, what, "more than 65535 long rows: raise long_threshold");
-        const size_t one = (size_t)n_long * a.piece_ld * sizeof(float);
-        if (!workspace || !aligned16(workspace) || workspace_bytes < one)
-            return fail(CTGCN_E_WORKSPACE, what, "long rows need a 16-byte aligned workspace of at least n_long * ctgcn_gat_piece_floats(d, heads) * 4 bytes (one piece per row)");
-        const size_t mp = workspace_bytes / one;
-        a.max_pieces = (int32_t)(mp > 4096 ? 4096 : mp);
-        a.part = (float *)workspace;
-    }
-    return CTGCN_OK;
+    return set_long_rows(a, what, long_rows, n_long, long_threshold, a.piece_ld, workspace, workspace_bytes,
+                         "long rows need a 16-byte aligned workspace of at least n_long * ctgcn_gat_piece_floats(d, heads) * 4 bytes (one piece per row)");
 }
 
 bool bad_scalars(const char *what, double alpha, double p_att, double p_feat, int32_t epi, int &rc)
 {
     rc = CTGCN_OK;
-    if (!std::isfinite(alpha)) rc = fail(CTGCN_E_INVALID, what, "alpha not finite");
-    else if (bad_p(p_att) || bad_p(p_feat)) rc = fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
-    else if (epi != EPI_NONE && epi != EPI_ELU && epi != EPI_ELU_DROP) rc = fail(CTGCN_E_INVALID, what, "epi must be 0 (none), 1 (ELU) or 2 (ELU + feature dropout)");
+    if (!std::isfinite(alpha)) rc = ctgcn_fail(CTGCN_E_INVALID, what, "alpha not finite");
+    else if (bad_p(p_att) || bad_p(p_feat)) rc = ctgcn_fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
+    else if (epi != EPI_NONE && epi != EPI_ELU && epi != EPI_ELU_DROP) rc = ctgcn_fail(CTGCN_E_INVALID, what, "epi must be 0 (none), 1 (ELU) or 2 (ELU + feature dropout)");
     return rc != CTGCN_OK;
 }
 
@@ -619,9 +549,9 @@ extern "C" int ctgcn_gat_fwd_f32(int64_t n, int32_t d, int32_t heads, const int3
     int rc = check_shape(what, n, d, heads);
     if (rc < 0) return rc;
     if (bad_scalars(what, alpha, p_att, p_feat, epi, rc)) return rc;
-    if (lds < d || ldout < d || (epi != EPI_NONE && ldy < d)) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (lds < d || ldout < d || (epi != EPI_NONE && ldy < d)) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     if (n == 0) return CTGCN_OK;
-    if (!S || !a_src || !a_dst || !out || !u || !v || !m || !Z || (epi != EPI_NONE && !Y)) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!S || !a_src || !a_dst || !out || !u || !v || !m || !Z || (epi != EPI_NONE && !Y)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     GatArgs a{};
     if ((rc = set_gather(a, what, n, d, heads, row_ptr, col, alpha, p_att, key, long_rows, n_long, long_threshold, workspace, workspace_bytes))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -650,10 +580,10 @@ extern "C" int ctgcn_gat_bwd_prep_f32(int64_t n, int32_t d, int32_t heads, const
     int rc = check_shape(what, n, d, heads);
     if (rc < 0) return rc;
     if (bad_scalars(what, 0.0, 0.0, p_feat, epi, rc)) return rc;
-    if (lddy < d || ldy < d || (epi != EPI_NONE && ldg < d)) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (lddy < d || ldy < d || (epi != EPI_NONE && ldg < d)) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     if (n == 0) return CTGCN_OK;
-    if (!dY || !Y || !u || !m || !Z || !pack || (epi != EPI_NONE && !G)) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (!aligned16(pack)) return fail(CTGCN_E_INVALID, what, "pack must be 16-byte aligned");
+    if (!dY || !Y || !u || !m || !Z || !pack || (epi != EPI_NONE && !G)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!ctgcn_aligned16(pack)) return ctgcn_fail(CTGCN_E_INVALID, what, "pack must be 16-byte aligned");
     PairArgs s{};
     s.heads = heads; s.F = d / heads; s.X = dY; s.ldx = lddy; s.Y = Y; s.ldy = ldy; s.s1 = u; s.s2 = m; s.s3 = Z; s.pack = (f4 *)pack;
     s.G = epi != EPI_NONE ? G : nullptr; s.ldg = ldg; s.epi = epi; s.fdrop = epi == EPI_ELU_DROP && p_feat > 0.0; s.p_feat = p_feat;
@@ -670,10 +600,10 @@ extern "C" int ctgcn_gat_bwd_row_f32(int64_t n, int32_t d, int32_t heads, const 
     int rc = check_shape(what, n, d, heads);
     if (rc < 0) return rc;
     if (bad_scalars(what, alpha, p_att, 0.0, EPI_NONE, rc)) return rc;
-    if (lds < d || ldg < d || ldr < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (lds < d || ldg < d || ldr < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     if (n == 0) return CTGCN_OK;
-    if (!S || !G || !v || !pack || !R || !csum || !du) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (!aligned16(pack)) return fail(CTGCN_E_INVALID, what, "pack must be 16-byte aligned");
+    if (!S || !G || !v || !pack || !R || !csum || !du) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!ctgcn_aligned16(pack)) return ctgcn_fail(CTGCN_E_INVALID, what, "pack must be 16-byte aligned");
     GatArgs a{};
     if ((rc = set_gather(a, what, n, d, heads, row_ptr, col, alpha, p_att, key, long_rows, n_long, long_threshold, workspace, workspace_bytes))) return rc;
     a.src = S; a.ldsrc = lds; a.v = v; a.pack = (const f4 *)pack; a.out1 = R; a.ld1 = ldr; a.sout = csum;
@@ -693,11 +623,11 @@ extern "C" int ctgcn_gat_bwd_col_f32(int64_t n, int32_t d, int32_t heads, const 
     int rc = check_shape(what, n, d, heads);
     if (rc < 0) return rc;
     if (bad_scalars(what, alpha, p_att, 0.0, EPI_NONE, rc)) return rc;
-    if (lds < d || ldg < d || ldb < d || (dS && ldds < d)) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
-    if ((dS == nullptr) != (du == nullptr)) return fail(CTGCN_E_INVALID, what, "du and dS go together");
+    if (lds < d || ldg < d || ldb < d || (dS && ldds < d)) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if ((dS == nullptr) != (du == nullptr)) return ctgcn_fail(CTGCN_E_INVALID, what, "du and dS go together");
     if (n == 0) return CTGCN_OK;
-    if (!S || !G || !v || !pack || !B || !ksum || !dv || (dS && (!a_src || !a_dst))) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (!aligned16(pack)) return fail(CTGCN_E_INVALID, what, "pack must be 16-byte aligned");
+    if (!S || !G || !v || !pack || !B || !ksum || !dv || (dS && (!a_src || !a_dst))) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!ctgcn_aligned16(pack)) return ctgcn_fail(CTGCN_E_INVALID, what, "pack must be 16-byte aligned");
     GatArgs a{};
     if ((rc = set_gather(a, what, n, d, heads, row_ptr, col, alpha, p_att, key, long_rows, n_long, long_threshold, workspace, workspace_bytes))) return rc;
     a.src = G; a.ldsrc = ldg; a.v = v; a.pack = (const f4 *)pack; a.out1 = dS; a.ld1 = ldds; a.out2 = B; a.ld2 = ldb; a.sout = ksum;
@@ -720,18 +650,18 @@ extern "C" int ctgcn_gat_da_f32(int64_t n, int32_t d, int32_t heads, const float
     const char *what = "gat_da";
     int rc = check_shape(what, n, d, heads);
     if (rc < 0) return rc;
-    if (lds < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
-    if ((du == nullptr) != (da_src == nullptr) || (dv == nullptr) != (da_dst == nullptr)) return fail(CTGCN_E_INVALID, what, "du goes with da_src, dv with da_dst");
-    if (!du && !dv) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (lds < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if ((du == nullptr) != (da_src == nullptr) || (dv == nullptr) != (da_dst == nullptr)) return ctgcn_fail(CTGCN_E_INVALID, what, "du goes with da_src, dv with da_dst");
+    if (!du && !dv) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {                                                 // empty sums
         if (da_src) CTGCN_TRY(hipMemsetAsync(da_src, 0, (size_t)d * sizeof(float), st));
         if (da_dst) CTGCN_TRY(hipMemsetAsync(da_dst, 0, (size_t)d * sizeof(float), st));
         return CTGCN_OK;
     }
-    if (!S) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!S) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     if (!workspace || workspace_bytes < ctgcn_gat_da_workspace_bytes(n, d))
-        return fail(CTGCN_E_WORKSPACE, what, "workspace must hold ctgcn_gat_da_workspace_bytes() bytes");
+        return ctgcn_fail(CTGCN_E_WORKSPACE, what, "workspace must hold ctgcn_gat_da_workspace_bytes() bytes");
     const int64_t blocks = (n + DA_ROWS - 1) / DA_ROWS;
     const int32_t part_ld = (d + 3) & ~3;
     hipLaunchKernelGGL(gat_da_kernel, dim3((unsigned)blocks, (unsigned)((d + 63) / 64)), dim3(64 * DA_WAVES), 0, st, n, d, heads, d / heads, S, lds, du, dv, part_ld, (float *)workspace);

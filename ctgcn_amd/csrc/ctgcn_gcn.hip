@@ -5,11 +5,11 @@
 //   forward     Y[i] = act(sum_e val[e] S[col[e]]), optionally scores[i] = Y[i] · p for the next layer's top-k.
 //   backward    dS[i] = sum_e val[e] (dY[col[e]] ∘ m(Y[col[e]])) over the same (symmetric) CSR; the mask is formed on the gathered row.
 //
-// Pull form: a group of LPR lanes owns a destination row and a float4 (or a float) per lane of it, the row's entries are read LPR at a
-// time and handed round by shuffles, four gathered rows in flight per group.  Rows longer than long_threshold entries are left to a
-// block-per-piece kernel: a piece is at most 4 long_threshold entries, its eight lane groups sum interleaved entries and are added in
-// group order, the pieces of a row are added in piece order by a last kernel that also finishes the row.  No atomics: every sum has a
-// fixed order, so repeated launches are bit-identical.
+// Pull form (the scaffold and its contract: ctgcn_gather.h): a group of LPR lanes owns a destination row and a float4 (or a float) per
+// lane of it, the row's entries are read LPR at a time and handed round by shuffles, four gathered rows in flight per group.  Rows
+// longer than long_threshold entries are left to a block-per-piece kernel: a piece is at most 4 long_threshold entries, its eight lane
+// groups sum interleaved entries and are added in group order, the pieces of a row are added in piece order by a last kernel that also
+// finishes the row.  No atomics: every sum has a fixed order, so repeated launches are bit-identical.
 //
 // The GCN step of the GCN / GCRN baselines (reference baseline/gcn.py:36-43 and :84-88, baseline/gcrn.py:56-57) is the same gather with
 // an epilogue on the finished row:
@@ -21,29 +21,16 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdio>
-#include <initializer_list>
 
+#include "ctgcn_gather.h"
 #include "ctgcn_rng.h"
 #include "ctgcn_try.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 constexpr float RRELU_SLOPE = (float)((1.0 / 8.0 + 1.0 / 3.0) / 2.0);   // F.rrelu in eval mode: the mean of its default bounds
-constexpr int PIECE_FACTOR = 4;        // entries of a long row's piece, in units of long_threshold
-constexpr int PIECE_THREADS = 256;
-constexpr int PIECE_LANES = 32;        // lanes across the feature row in the piece kernel
-constexpr int PIECE_GROUPS = PIECE_THREADS / PIECE_LANES;
 constexpr int U = 4;                   // gathered rows in flight per lane group
 
-template <int VEC> struct vec_of;
-template <> struct vec_of<4> { using type = f4; };
-template <> struct vec_of<1> { using type = float; };
-
-__device__ __forceinline__ f4 vfma(float a, f4 x, f4 acc) { return f4{fmaf(a, x.x, acc.x), fmaf(a, x.y, acc.y), fmaf(a, x.z, acc.z), fmaf(a, x.w, acc.w)}; }
-__device__ __forceinline__ float vfma(float a, float x, float acc) { return fmaf(a, x, acc); }
 __device__ __forceinline__ float rrelu1(float y) { return y >= 0.f ? y : y * RRELU_SLOPE; }
 __device__ __forceinline__ f4 rrelu(f4 y) { return f4{rrelu1(y.x), rrelu1(y.y), rrelu1(y.z), rrelu1(y.w)}; }
 __device__ __forceinline__ float rrelu(float y) { return rrelu1(y); }
@@ -73,13 +60,6 @@ struct GcnArgs {
     int32_t part_ld;        // floats per partial vector: d rounded up to 4
     float *part;            // [n_long][max_pieces][part_ld]
 };
-
-__host__ __device__ __forceinline__ int pieces_of(int len, int long_thresh, int max_pieces)
-{
-    const int64_t piece = (int64_t)PIECE_FACTOR * long_thresh;
-    const int64_t np = (len + piece - 1) / piece;
-    return (int)(np < 1 ? 1 : (np > max_pieces ? max_pieces : np));
-}
 
 template <int VEC, bool BWD>
 __device__ __forceinline__ typename vec_of<VEC>::type gather_row(const GcnArgs &a, int64_t c, int64_t foff)
@@ -131,7 +111,6 @@ __device__ __forceinline__ typename vec_of<VEC>::type row_sum(const GcnArgs &a, 
 // ------------------------------------------------------------------------------------------------ epilogues on a finished row
 // 0..2 are ctgcn_gcn_conv_fwd_f32's epi argument; EPI_RRELU is the layer's act 1 and is not accepted there
 constexpr int EPI_NONE = 0, EPI_RELU = 1, EPI_L2NORM = 2, EPI_RRELU = 3;
-constexpr float L2_EPS = 1e-12f;       // F.normalize's eps: the denominator is max(norm, eps)
 
 struct GcnEpi {
     int32_t kind;
@@ -282,10 +261,7 @@ __global__ __launch_bounds__(64) void gcn_final_kernel(const GcnArgs a, const Gc
 }
 
 // ------------------------------------------------------------------------------------------------ GCN / GCRN step: backward pre-pass
-constexpr int PREP_ROWS = 64;          // rows of a block: one partial bias-gradient vector per block
-constexpr int PREP_WAVES = 4;          // wave w takes the block's rows w, w + 4, ...; its lanes lie across the feature row
-constexpr int DB_COLS = 32, DB_SEGS = 32;
-
+// PREP_ROWS rows a block, one partial bias-gradient vector per block; colsum_kernel (ctgcn_gather.h) adds them in block order
 struct PrepArgs {
     int64_t n;
     int32_t d, chunks, epi;
@@ -356,70 +332,14 @@ __global__ __launch_bounds__(64 * PREP_WAVES) void gcn_conv_prep_kernel(const Pr
     }
 }
 
-// db[c] = sum over the pre-pass blocks of part[b][c]: DB_SEGS runs of consecutive blocks, each in block order, then the runs in run order
-__global__ __launch_bounds__(DB_COLS * DB_SEGS) void gcn_conv_db_kernel(int64_t blocks, int32_t d, int32_t part_ld, const float *part, float *db)
-{
-    __shared__ float sm[DB_SEGS][DB_COLS];
-    const int cx = threadIdx.x % DB_COLS, seg = threadIdx.x / DB_COLS;
-    const int64_t c = (int64_t)blockIdx.x * DB_COLS + cx;
-    const int64_t per = (blocks + DB_SEGS - 1) / DB_SEGS;
-    const int64_t lo = min(blocks, seg * per), hi = min(blocks, lo + per);
-    float t = 0.f;
-    if (c < d)
-        for (int64_t b = lo; b < hi; ++b) t += part[b * part_ld + c];
-    sm[seg][cx] = t;
-    __syncthreads();
-    if (seg == 0 && c < d) {
-        for (int k = 1; k < DB_SEGS; ++k) t += sm[k][cx];
-        db[c] = t;
-    }
-}
-
-int fail(int code, const char *what, const char *text)
-{
-    char buf[192];
-    snprintf(buf, sizeof(buf), "%s: %s", what, text);
-    return ctgcn_set_error_(code, buf);
-}
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// p as [.][ld] rows, or a vector with ld 0; a null p is an operand the call does not have
-struct Operand {
-    const void *p;
-    int64_t ld;
-};
-
-// float4 rows: d and every leading dimension a multiple of 4, every base 16-byte aligned
-bool float4_rows(int32_t d, std::initializer_list<Operand> operands)
-{
-    if (d % 4) return false;
-    for (const Operand &o : operands)
-        if (o.p && (o.ld % 4 || !aligned16(o.p))) return false;
-    return true;
-}
-
 template <int VEC, bool BWD, int KIND>
 int launch(GcnArgs a, const GcnEpi &e, hipStream_t st)
 {
     a.chunks = (a.d + VEC - 1) / VEC;
-    const int lpr = a.chunks <= 4 ? 4 : a.chunks <= 8 ? 8 : a.chunks <= 16 ? 16 : a.chunks <= 32 ? 32 : 64;
-    const dim3 grid((unsigned)((a.n + 256 / lpr - 1) / (256 / lpr)));
-    switch (lpr) {
-    case 4: hipLaunchKernelGGL((gcn_row_kernel<VEC, 4, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
-    case 8: hipLaunchKernelGGL((gcn_row_kernel<VEC, 8, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
-    case 16: hipLaunchKernelGGL((gcn_row_kernel<VEC, 16, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
-    case 32: hipLaunchKernelGGL((gcn_row_kernel<VEC, 32, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
-    default: hipLaunchKernelGGL((gcn_row_kernel<VEC, 64, BWD, KIND>), grid, dim3(256), 0, st, a, e); break;
-    }
-    CTGCN_TRY(hipGetLastError());
-    if (a.n_long > 0) {
-        hipLaunchKernelGGL((gcn_piece_kernel<VEC, BWD>), dim3((unsigned)a.max_pieces, (unsigned)a.n_long), dim3(PIECE_THREADS), 0, st, a);
-        CTGCN_TRY(hipGetLastError());
-        hipLaunchKernelGGL(gcn_final_kernel, dim3((unsigned)a.n_long), dim3(64), 0, st, a, e);
-        CTGCN_TRY(hipGetLastError());
-    }
-    return CTGCN_OK;
+    return launch_rows(
+        a, [&](auto lpr, dim3 grid) { hipLaunchKernelGGL((gcn_row_kernel<VEC, decltype(lpr)::value, BWD, KIND>), grid, dim3(256), 0, st, a, e); },
+        [&](dim3 grid) { hipLaunchKernelGGL((gcn_piece_kernel<VEC, BWD>), grid, dim3(PIECE_THREADS), 0, st, a); },
+        [&](dim3 grid) { hipLaunchKernelGGL(gcn_final_kernel, grid, dim3(64), 0, st, a, e); });
 }
 
 // picks the launcher's instantiation for a call: float4 or scalar rows, the backward's masked gather or the forward with e.kind
@@ -439,29 +359,17 @@ int dispatch(const GcnArgs &a, const GcnEpi &e, bool bwd, bool v4, void *stream)
 int set_common(GcnArgs &a, const char *what, int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val,
                const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes)
 {
-    if (n < 0 || n > INT32_MAX || d < 1) return fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
-    if (n_long < 0 || n_long > n) return fail(CTGCN_E_INVALID, what, "n_long outside [0, n]");
+    if (n < 0 || n > INT32_MAX || d < 1) return ctgcn_fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
+    if (n_long < 0 || n_long > n) return ctgcn_fail(CTGCN_E_INVALID, what, "n_long outside [0, n]");
     if (n == 0) return CTGCN_OK;
-    if (!row_ptr || !col || !val) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!row_ptr || !col || !val) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     a.n = n; a.d = d; a.row_ptr = row_ptr; a.col = col; a.val = val;
-    a.long_rows = long_rows; a.n_long = n_long; a.long_thresh = long_threshold;
     a.part_ld = (d + 3) & ~3;
-    if (n_long > 0) {
-        if (!long_rows) return fail(CTGCN_E_INVALID, what, "n_long > 0 without long_rows");
-        if (long_threshold < 1 || long_threshold > INT32_MAX / PIECE_FACTOR) return fail(CTGCN_E_INVALID, what, "long_threshold outside [1, 2^29)");
-        if (n_long > 65535) return fail(CTGCN_E_UNSUPPORTED, what, "more than 65535 long rows: raise long_threshold");
-        const size_t one = (size_t)n_long * a.part_ld * sizeof(float);
-        if (!workspace || !aligned16(workspace) || workspace_bytes < one)
-            return fail(CTGCN_E_WORKSPACE, what, "long rows need a 16-byte aligned workspace of at least n_long * round_up(d, 4) * 4 bytes (one piece per row)");
-        const size_t mp = workspace_bytes / one;
-        a.max_pieces = (int32_t)(mp > 4096 ? 4096 : mp);
-        a.part = (float *)workspace;
-    }
-    return CTGCN_OK;
+    return set_long_rows(a, what, long_rows, n_long, long_threshold, a.part_ld, workspace, workspace_bytes,
+                         "long rows need a 16-byte aligned workspace of at least n_long * round_up(d, 4) * 4 bytes (one piece per row)");
 }
 
 bool bad_epi(int32_t epi) { return epi != EPI_NONE && epi != EPI_RELU && epi != EPI_L2NORM; }
-bool bad_p(double p) { return !(p >= 0.0 && p < 1.0); }
 
 // ------------------------------------------------------------------------------------------------ normalisation
 constexpr int NORM_LANES = 16;
@@ -503,12 +411,12 @@ extern "C" int ctgcn_gcn_normalize_f32(int64_t n, const int32_t *row_ptr, const 
                                        float *val_out, int32_t *flag, void *workspace, size_t workspace_bytes, void *stream)
 {
     const char *what = "gcn_normalize";
-    if (n < 0 || n > INT32_MAX) return fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31");
-    if (row_norm != 0 && row_norm != 1) return fail(CTGCN_E_INVALID, what, "row_norm must be 0 or 1");
+    if (n < 0 || n > INT32_MAX) return ctgcn_fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31");
+    if (row_norm != 0 && row_norm != 1) return ctgcn_fail(CTGCN_E_INVALID, what, "row_norm must be 0 or 1");
     if (n == 0) return CTGCN_OK;
-    if (!row_ptr || !col || !val_in || !val_out || !flag) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!row_ptr || !col || !val_in || !val_out || !flag) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7) || workspace_bytes < ctgcn_gcn_normalize_workspace_bytes(n))
-        return fail(CTGCN_E_WORKSPACE, what, "workspace must be 8-byte aligned and hold ctgcn_gcn_normalize_workspace_bytes() bytes");
+        return ctgcn_fail(CTGCN_E_WORKSPACE, what, "workspace must be 8-byte aligned and hold ctgcn_gcn_normalize_workspace_bytes() bytes");
     hipStream_t st = (hipStream_t)stream;
     double *r = (double *)workspace;
     const unsigned grid = (unsigned)((n + 256 / NORM_LANES - 1) / (256 / NORM_LANES));
@@ -527,12 +435,12 @@ extern "C" int ctgcn_gcn_layer_fwd_f32(int64_t n, int32_t d, const int32_t *row_
 {
     const char *what = "gcn_layer_fwd";
     GcnArgs a{};
-    if (act != 0 && act != 1) return fail(CTGCN_E_INVALID, what, "act must be 0 (identity) or 1 (eval-mode RReLU)");
-    if (lds < d || ldy < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
-    if ((score_vec == nullptr) != (score_out == nullptr)) return fail(CTGCN_E_INVALID, what, "score_vec and score_out go together");
+    if (act != 0 && act != 1) return ctgcn_fail(CTGCN_E_INVALID, what, "act must be 0 (identity) or 1 (eval-mode RReLU)");
+    if (lds < d || ldy < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if ((score_vec == nullptr) != (score_out == nullptr)) return ctgcn_fail(CTGCN_E_INVALID, what, "score_vec and score_out go together");
     if (int rc = set_common(a, what, n, d, row_ptr, col, val, long_rows, n_long, long_threshold, workspace, workspace_bytes)) return rc;
     if (n == 0) return CTGCN_OK;
-    if (!S || !Y) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!S || !Y) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     a.src = S; a.ldsrc = lds; a.out = Y; a.ldout = ldy;
     GcnEpi e{};
     e.kind = act ? EPI_RRELU : EPI_NONE; e.score_vec = score_vec; e.score_out = score_out;
@@ -546,11 +454,11 @@ extern "C" int ctgcn_gcn_layer_bwd_f32(int64_t n, int32_t d, const int32_t *row_
 {
     const char *what = "gcn_layer_bwd";
     GcnArgs a{};
-    if (act != 0 && act != 1) return fail(CTGCN_E_INVALID, what, "act must be 0 (identity) or 1 (eval-mode RReLU)");
-    if (lddy < d || ldds < d || (act && ldy < d)) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (act != 0 && act != 1) return ctgcn_fail(CTGCN_E_INVALID, what, "act must be 0 (identity) or 1 (eval-mode RReLU)");
+    if (lddy < d || ldds < d || (act && ldy < d)) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     if (int rc = set_common(a, what, n, d, row_ptr, col, val, long_rows, n_long, long_threshold, workspace, workspace_bytes)) return rc;
     if (n == 0) return CTGCN_OK;
-    if (!dY || !dS || (act && !Y)) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!dY || !dS || (act && !Y)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     a.src = dY; a.ldsrc = lddy; a.ymask = act ? Y : nullptr; a.ldmask = act ? ldy : 0; a.out = dS; a.ldout = ldds;
     return dispatch(a, GcnEpi{}, true, float4_rows(d, {{dY, lddy}, {dS, ldds}, {a.ymask, ldy}}), stream);
 }
@@ -562,12 +470,12 @@ extern "C" int ctgcn_gcn_conv_fwd_f32(int64_t n, int32_t d, const int32_t *row_p
 {
     const char *what = "gcn_conv_fwd";
     GcnArgs a{};
-    if (bad_epi(epi)) return fail(CTGCN_E_INVALID, what, "epi must be 0 (none), 1 (ReLU + dropout) or 2 (L2 row normalisation)");
-    if (bad_p(p)) return fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
-    if (lds < d || ldy < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (bad_epi(epi)) return ctgcn_fail(CTGCN_E_INVALID, what, "epi must be 0 (none), 1 (ReLU + dropout) or 2 (L2 row normalisation)");
+    if (bad_p(p)) return ctgcn_fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
+    if (lds < d || ldy < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     if (int rc = set_common(a, what, n, d, row_ptr, col, val, long_rows, n_long, long_threshold, workspace, workspace_bytes)) return rc;
     if (n == 0) return CTGCN_OK;
-    if (!S || !Y || (epi == EPI_L2NORM && !norm)) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!S || !Y || (epi == EPI_L2NORM && !norm)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     a.src = S; a.ldsrc = lds; a.out = Y; a.ldout = ldy;
     GcnEpi e{};
     e.kind = epi; e.bias = bias; e.norm = norm; e.drop = epi == EPI_RELU && p > 0.0; e.p = p; e.scale = 1.0f / (1.0f - (float)p); e.key = key;
@@ -587,15 +495,15 @@ extern "C" int ctgcn_gcn_conv_prep_f32(int64_t n, int32_t d, const float *dY, in
                                        void *stream)
 {
     const char *what = "gcn_conv_prep";
-    if (n < 0 || n > INT32_MAX || d < 1) return fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
-    if (bad_epi(epi)) return fail(CTGCN_E_INVALID, what, "epi must be 0 (none), 1 (ReLU + dropout) or 2 (L2 row normalisation)");
-    if (bad_p(p)) return fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
+    if (n < 0 || n > INT32_MAX || d < 1) return ctgcn_fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
+    if (bad_epi(epi)) return ctgcn_fail(CTGCN_E_INVALID, what, "epi must be 0 (none), 1 (ReLU + dropout) or 2 (L2 row normalisation)");
+    if (bad_p(p)) return ctgcn_fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
     if (n == 0) return CTGCN_OK;
     const bool wants_g = epi != EPI_NONE;
-    if (!dY || (wants_g && (!Y || !G)) || (epi == EPI_L2NORM && !norm)) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (lddy < d || (wants_g && (ldy < d || ldg < d))) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
-    if (db && (!workspace || !aligned16(workspace) || workspace_bytes < ctgcn_gcn_conv_prep_workspace_bytes(n, d)))
-        return fail(CTGCN_E_WORKSPACE, what, "a bias gradient needs a 16-byte aligned workspace of ctgcn_gcn_conv_prep_workspace_bytes() bytes");
+    if (!dY || (wants_g && (!Y || !G)) || (epi == EPI_L2NORM && !norm)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (lddy < d || (wants_g && (ldy < d || ldg < d))) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (db && (!workspace || !ctgcn_aligned16(workspace) || workspace_bytes < ctgcn_gcn_conv_prep_workspace_bytes(n, d)))
+        return ctgcn_fail(CTGCN_E_WORKSPACE, what, "a bias gradient needs a 16-byte aligned workspace of ctgcn_gcn_conv_prep_workspace_bytes() bytes");
     if (!wants_g && !db) return CTGCN_OK;                          // G = dY and no column sums: nothing to write
     PrepArgs a{};
     a.n = n; a.d = d; a.epi = epi; a.dY = dY; a.lddy = lddy; a.Y = wants_g ? Y : nullptr; a.ldy = ldy; a.norm = norm;
@@ -609,7 +517,7 @@ extern "C" int ctgcn_gcn_conv_prep_f32(int64_t n, int32_t d, const float *dY, in
     else hipLaunchKernelGGL(gcn_conv_prep_kernel<1>, dim3((unsigned)blocks), dim3(64 * PREP_WAVES), 0, st, a);
     CTGCN_TRY(hipGetLastError());
     if (db) {
-        hipLaunchKernelGGL(gcn_conv_db_kernel, dim3((unsigned)((d + DB_COLS - 1) / DB_COLS)), dim3(DB_COLS * DB_SEGS), 0, st, blocks, d, a.part_ld,
+        hipLaunchKernelGGL((colsum_kernel<DB_COLS, DB_SEGS>), dim3((unsigned)((d + DB_COLS - 1) / DB_COLS)), dim3(DB_COLS * DB_SEGS), 0, st, blocks, d, a.part_ld,
                            (const float *)a.part, db);
         CTGCN_TRY(hipGetLastError());
     }

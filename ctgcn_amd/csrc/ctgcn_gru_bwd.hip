@@ -501,7 +501,6 @@ int device_cus(int *cus)
     *cus = ctgcn_persistent_cus_(*cus);
     return CTGCN_OK;
 }
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 int ablate_mask() { static const int m = [] { const char *e = getenv("CTGCN_BWD_ABLATE"); return e ? atoi(e) : 0; }(); return m; }
 
 }  // namespace
@@ -524,7 +523,7 @@ int ctgcn_gru_bwd_rec_f32(int64_t rows, int32_t steps, int32_t hidden, const flo
     if (rows < 0 || steps < 1 || steps > 64 || (gate_count != 3 && gate_count != 4)) return ctgcn_set_error_(CTGCN_E_INVALID, "gru_bwd_rec: bad sizes (1 <= steps <= 64, gate_count 3 or 4)");
     if (!gates || !h_seq || !w_hh || !d_gi || !dw_partial || !dbn_partial || ((dh_sum == nullptr) == (dh_seq == nullptr)))
         return ctgcn_set_error_(CTGCN_E_INVALID, "gru_bwd_rec: null pointer (exactly one of dh_sum / dh_seq)");
-    if (!aligned16(gates) || !aligned16(h_seq) || !aligned16(dh_sum) || !aligned16(dh_seq) || !aligned16(d_gi) || !aligned16(dw_partial) || !aligned16(dbn_partial))
+    if (!ctgcn_aligned16(gates) || !ctgcn_aligned16(h_seq) || !ctgcn_aligned16(dh_sum) || !ctgcn_aligned16(dh_seq) || !ctgcn_aligned16(d_gi) || !ctgcn_aligned16(dw_partial) || !ctgcn_aligned16(dbn_partial))
         return ctgcn_set_error_(CTGCN_E_INVALID, "gru_bwd_rec: buffers must be 16-byte aligned");
     const int32_t blocks = ctgcn_gru_bwd_blocks(rows);
     if (n_partial < blocks) return ctgcn_set_error_(CTGCN_E_INVALID, "gru_bwd_rec: n_partial < ctgcn_gru_bwd_blocks(rows)");
@@ -550,7 +549,7 @@ int ctgcn_gru_bwd_in_f32(int64_t rows, int32_t steps, int32_t hidden, const floa
     if (rows < 0 || steps < 1 || steps > 64) return ctgcn_set_error_(CTGCN_E_INVALID, "gru_bwd_in: bad sizes (1 <= steps <= 64)");
     if (!d_gi || !w_ih || !dw_partial || !dbi_partial || ((x_planes == nullptr) == (x == nullptr)) || ((dx == nullptr) == (Z == nullptr)))
         return ctgcn_set_error_(CTGCN_E_INVALID, "gru_bwd_in: null pointer (exactly one of x_planes / x and of dx / Z)");
-    if (!aligned16(d_gi) || !aligned16(x) || !aligned16(dx) || !aligned16(Z) || !aligned16(S0) || !aligned16(dw_partial) || !aligned16(dbi_partial) ||
+    if (!ctgcn_aligned16(d_gi) || !ctgcn_aligned16(x) || !ctgcn_aligned16(dx) || !ctgcn_aligned16(Z) || !ctgcn_aligned16(S0) || !ctgcn_aligned16(dw_partial) || !ctgcn_aligned16(dbi_partial) ||
         (reinterpret_cast<uintptr_t>(x_planes) & 7u) || (x && (ldx < GH || (ldx & 3))))
         return ctgcn_set_error_(CTGCN_E_INVALID, "gru_bwd_in: buffers must be 16-byte aligned (planes 8), ldx a multiple of 4 and >= 128");
     if (x_planes && (first_row < 0 || (first_row & 15) || plane_rows < (first_row + rows) * steps))

@@ -541,8 +541,6 @@ AggPlan plan_for(int d, bool vec4_ok)
     return p;
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // CUs a persistent kernel (one block per CU) may count on: the device's, or fewer when the caller runs it on a stream with a CU mask
 // (ctgcn_set_persistent_cus: the snapshot pipeline gives the HBM-bound aggregation its own few CUs next to the matrix-core kernels)
 // (round 4's gru_layer8_h2_pair_kernel — two tiles in flight per block, the two waves of a SIMD half a step out of phase — was bit-identical and
@@ -4285,7 +4283,7 @@ int ctgcn_transpose_bias_f32(int64_t n, int32_t d, const float *w, int64_t ldw, 
     if (n == 0) return CTGCN_OK;
     if (!w || !out) return fail(CTGCN_E_INVALID, "transpose_bias: null pointer");
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)((d + 63) / 64));
-    if (!(ldw & 3) && !(ldo & 3) && aligned16(w) && aligned16(out))
+    if (!(ldw & 3) && !(ldo & 3) && ctgcn_aligned16(w) && ctgcn_aligned16(out))
         hipLaunchKernelGGL(transpose_bias_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, n, d, w, ldw, bias, out, ldo);
     else
         hipLaunchKernelGGL(transpose_bias_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, n, d, w, ldw, bias, out, ldo);
@@ -4305,7 +4303,7 @@ int ctgcn_spmm_csr_f32(int64_t n_rows, int32_t d, const int32_t *row_ptr, const 
     a.row_ptr = row_ptr; a.col = col_idx; a.val = val; a.slot = nullptr;
     a.src = X; a.ldsrc = ldx; a.self = nullptr; a.out = Y; a.out_ld = ldy;
     a.flags = CTGCN_F_NESTED; a.accumulate = accumulate ? 1 : 0;
-    const bool v4 = (d % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && aligned16(X) && aligned16(Y);
+    const bool v4 = (d % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && ctgcn_aligned16(X) && ctgcn_aligned16(Y);
     return launch_agg<true>(a, v4, (hipStream_t)stream);
 }
 
@@ -4328,7 +4326,7 @@ int ctgcn_core_aggregate_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t
     a.long_rows = long_rows; a.n_long = n_long; a.long_thresh = long_threshold;
     if (n_long > 0 && long_threshold < 1) return fail(CTGCN_E_INVALID, "core_aggregate: long_threshold must be >= 1");
     if (int rc = set_hub_pieces(a, K, hub_split, hub_workspace, hub_workspace_bytes, "core_aggregate")) return rc;
-    const bool v4 = (d % 4 == 0) && (ldx % 4 == 0) && aligned16(X) && aligned16(H);
+    const bool v4 = (d % 4 == 0) && (ldx % 4 == 0) && ctgcn_aligned16(X) && ctgcn_aligned16(H);
     return launch_agg<true>(a, v4, (hipStream_t)stream);
 }
 
@@ -4352,7 +4350,7 @@ int ctgcn_core_aggregate_split_f32(int64_t n_rows, int32_t d, int32_t K, const i
     if (n_rows == 0) return CTGCN_OK;
     if (!row_ptr || !X || !workspace) return fail(CTGCN_E_INVALID, "core_aggregate_split: null pointer");
     if (!slot && K != 1) return fail(CTGCN_E_INVALID, "core_aggregate_split: slot tags required when K > 1");
-    if ((d & 3) || d > 512 || (ldx & 3) || !aligned16(X) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+    if ((d & 3) || d > 512 || (ldx & 3) || !ctgcn_aligned16(X) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
         return fail(CTGCN_E_UNSUPPORTED, "core_aggregate_split: needs d %% 4 == 0, d <= 512, 16-byte aligned rows, 256-byte aligned workspace");
     if (n_long < 0 || (n_long > 0 && (!long_rows || long_threshold < 1))) return fail(CTGCN_E_INVALID, "core_aggregate_split: bad hub row list");
     if ((row_order == nullptr) != (tile_mask == nullptr)) return fail(CTGCN_E_INVALID, "core_aggregate_split: row_order and tile_mask come together");
@@ -4433,7 +4431,7 @@ int ctgcn_core_aggregate_bwd_prep_f32(int64_t n_rows, int32_t d, int32_t K, cons
     if (n_rows < 0 || d <= 0 || K < 1 || K > CTGCN_MAX_SLOTS) return fail(CTGCN_E_INVALID, "bwd_prep: bad sizes");
     if (n_rows == 0) return CTGCN_OK;
     if (!dH || !Z || ((flags & CTGCN_F_RELU) && !H)) return fail(CTGCN_E_INVALID, "bwd_prep: null pointer");
-    const bool v4 = (d % 4 == 0) && aligned16(dH) && aligned16(Z) && (!H || aligned16(H)) && (!S0 || aligned16(S0));
+    const bool v4 = (d % 4 == 0) && ctgcn_aligned16(dH) && ctgcn_aligned16(Z) && (!H || ctgcn_aligned16(H)) && (!S0 || ctgcn_aligned16(S0));
     const int vec = v4 ? 4 : 1;
     const int chunks = (d + vec - 1) / vec;
     const int64_t total = n_rows * chunks;
@@ -4466,7 +4464,7 @@ int ctgcn_core_aggregate_bwd_f32(int64_t n_rows, int32_t d, int32_t K, const int
     a.long_rows = long_rows; a.n_long = n_long; a.long_thresh = long_threshold;
     if (n_long > 0 && long_threshold < 1) return fail(CTGCN_E_INVALID, "core_aggregate_bwd: long_threshold must be >= 1");
     if (int rc = set_hub_pieces(a, 1, hub_split, hub_workspace, hub_workspace_bytes, "core_aggregate_bwd")) return rc;
-    const bool v4 = (d % 4 == 0) && (lddx % 4 == 0) && aligned16(Z) && aligned16(dX) && (!a.self || aligned16(a.self));
+    const bool v4 = (d % 4 == 0) && (lddx % 4 == 0) && ctgcn_aligned16(Z) && ctgcn_aligned16(dX) && (!a.self || ctgcn_aligned16(a.self));
     return launch_agg<false>(a, v4, (hipStream_t)stream);
 }
 
@@ -4643,7 +4641,7 @@ int ctgcn_gru_seq_f32(int64_t rows, int32_t steps, int32_t hidden, const float *
     if (rows < 0 || steps < 1) return fail(CTGCN_E_INVALID, "gru_seq: bad sizes rows=%lld steps=%d", (long long)rows, steps);
     if (rows == 0) return CTGCN_OK;
     if (!gi || !w_hh || !out) return fail(CTGCN_E_INVALID, "gru_seq: null pointer");
-    if (!aligned16(w_hh) || (reinterpret_cast<uintptr_t>(out) & 7u) || (ln_weight && (reinterpret_cast<uintptr_t>(ln_weight) & 7u)))
+    if (!ctgcn_aligned16(w_hh) || (reinterpret_cast<uintptr_t>(out) & 7u) || (ln_weight && (reinterpret_cast<uintptr_t>(ln_weight) & 7u)))
         return fail(CTGCN_E_INVALID, "gru_seq: w_hh must be 16-byte aligned, out / ln_weight 8-byte aligned");
     GruArgs a{};
     a.rows = rows; a.steps = steps; a.gi = gi; a.whh = w_hh; a.bhn = b_hn; a.gamma = ln_weight; a.beta = ln_bias;
@@ -4710,11 +4708,11 @@ int ctgcn_gru_layer_f32(int64_t rows, int32_t steps, int32_t d_in, int32_t hidde
     if (step_offsets && steps > 32) return fail(CTGCN_E_UNSUPPORTED, "gru_layer: step_offsets cover at most 32 steps (got %d)", steps);
     if (hidden != GRU_H || d_in != GRU_H) return fail(CTGCN_E_UNSUPPORTED, "gru_layer: only d_in = hidden = %d is built (got %d, %d)", GRU_H, d_in, hidden);
     if (gates_out && (reduce_sum || ln_weight)) return fail(CTGCN_E_INVALID, "gru_layer: gates_out needs reduce_sum == 0 and no LayerNorm (raw h sequence)");
-    if (gates_out && !aligned16(gates_out)) return fail(CTGCN_E_INVALID, "gru_layer: gates_out must be 16-byte aligned");
+    if (gates_out && !ctgcn_aligned16(gates_out)) return fail(CTGCN_E_INVALID, "gru_layer: gates_out must be 16-byte aligned");
     if (rows < 0 || steps < 1 || ldx < d_in) return fail(CTGCN_E_INVALID, "gru_layer: bad sizes rows=%lld steps=%d ldx=%lld", (long long)rows, steps, (long long)ldx);
     if (rows == 0) return CTGCN_OK;
     if (!x || !w_ih || !w_hh || !out) return fail(CTGCN_E_INVALID, "gru_layer: null pointer");
-    if (!aligned16(x) || !aligned16(w_ih) || !aligned16(w_hh) || (ldx % 4) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
+    if (!ctgcn_aligned16(x) || !ctgcn_aligned16(w_ih) || !ctgcn_aligned16(w_hh) || (ldx % 4) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
         (ln_weight && (reinterpret_cast<uintptr_t>(ln_weight) & 7u)) || (ln_bias && (reinterpret_cast<uintptr_t>(ln_bias) & 7u)))
         return fail(CTGCN_E_INVALID, "gru_layer: x / weights must be 16-byte aligned, ldx a multiple of 4, out / LayerNorm vectors 8-byte aligned");
     const int64_t ldo = ld_out > 0 ? ld_out : GRU_H;
@@ -4780,7 +4778,7 @@ int ctgcn_gru_layer_presplit_f32(int64_t rows, int32_t steps, int32_t hidden, co
     if (rows < 0 || steps < 1) return fail(CTGCN_E_INVALID, "gru_layer_presplit: bad sizes rows=%lld steps=%d", (long long)rows, steps);
     if (rows == 0) return CTGCN_OK;
     if (!planes || !w_ih || !w_hh || !out) return fail(CTGCN_E_INVALID, "gru_layer_presplit: null pointer");
-    if ((reinterpret_cast<uintptr_t>(planes) & 255u) || !aligned16(w_ih) || !aligned16(w_hh) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
+    if ((reinterpret_cast<uintptr_t>(planes) & 255u) || !ctgcn_aligned16(w_ih) || !ctgcn_aligned16(w_hh) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
         (ln_weight && (reinterpret_cast<uintptr_t>(ln_weight) & 7u)) || (ln_bias && (reinterpret_cast<uintptr_t>(ln_bias) & 7u)))
         return fail(CTGCN_E_INVALID, "gru_layer_presplit: planes 256-byte, weights 16-byte, out / LayerNorm vectors 8-byte aligned");
     const int64_t ldo = ld_out > 0 ? ld_out : GRU_H;
@@ -4825,7 +4823,7 @@ int ctgcn_gru_layer_presplit_save_f32(int64_t rows, int32_t steps, int32_t hidde
     if (tile_mask && steps > 64) return fail(CTGCN_E_UNSUPPORTED, "gru_layer_presplit_save: a row plan needs steps <= 64");
     if (rows == 0) return CTGCN_OK;
     if (!planes || !w_ih || !w_hh || !gates_out || !hseq_out || !presum_out) return fail(CTGCN_E_INVALID, "gru_layer_presplit_save: null pointer");
-    if ((reinterpret_cast<uintptr_t>(planes) & 255u) || !aligned16(w_ih) || !aligned16(w_hh) || !aligned16(gates_out) || !aligned16(hseq_out) || !aligned16(presum_out))
+    if ((reinterpret_cast<uintptr_t>(planes) & 255u) || !ctgcn_aligned16(w_ih) || !ctgcn_aligned16(w_hh) || !ctgcn_aligned16(gates_out) || !ctgcn_aligned16(hseq_out) || !ctgcn_aligned16(presum_out))
         return fail(CTGCN_E_INVALID, "gru_layer_presplit_save: planes 256-byte, everything else 16-byte aligned");
     int dev = 0, cus = 256;
     HIP_TRY(hipGetDevice(&dev));
@@ -4875,7 +4873,7 @@ int ctgcn_core_aggregate_split_group_f32(int32_t groups, int64_t n_rows, int32_t
     const bool layer_form = d == GRU_H && !g[0].planes1;      // consumer = the GRU layer kernel: planes with holes in the group's own workspace
     for (int i = 0; i < groups; ++i) {
         const ctgcn_agg_split_group_t &q = g[i];
-        if (q.K < 1 || q.K > CTGCN_MAX_SLOTS || !q.row_ptr || !q.X || (!q.slot && q.K != 1) || q.ldx < d || (q.ldx & 3) || !aligned16(q.X))
+        if (q.K < 1 || q.K > CTGCN_MAX_SLOTS || !q.row_ptr || !q.X || (!q.slot && q.K != 1) || q.ldx < d || (q.ldx & 3) || !ctgcn_aligned16(q.X))
             return fail(CTGCN_E_INVALID, "core_aggregate_split_group: bad arguments of group %d", i);
         if ((q.row_order == nullptr) != (q.tile_mask == nullptr) || (q.row_order && q.K > 32))
             return fail(CTGCN_E_INVALID, "core_aggregate_split_group: group %d: row_order and tile_mask come together, K <= 32 under a plan", i);
@@ -4931,7 +4929,7 @@ int ctgcn_transpose_bias_group_f32(int32_t groups, int64_t n, int32_t d, const f
     for (int i = 0; i < groups; ++i) {
         if (!w[i] || !out[i]) return fail(CTGCN_E_INVALID, "transpose_bias_group: null pointer in group %d", i);
         host[i] = TransposeGroup{w[i], bias ? bias[i] : nullptr, out[i]};
-        vec = vec && aligned16(w[i]) && aligned16(out[i]);
+        vec = vec && ctgcn_aligned16(w[i]) && ctgcn_aligned16(out[i]);
     }
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(ctgcn_table::upload(table, host.data(), host.size() * sizeof(TransposeGroup), shadow, st));
@@ -4960,7 +4958,7 @@ int ctgcn_gru_seq_group_f32(int32_t groups, int64_t rows, int32_t hidden, const 
     double total = 0.0;
     for (int i = 0; i < groups; ++i) {
         const ctgcn_gru_seq_group_t &q = g[i];
-        if (q.steps < 1 || !q.gi || !q.w_hh || !q.out || !aligned16(q.gi) || !aligned16(q.w_hh) || (reinterpret_cast<uintptr_t>(q.out) & 7u) ||
+        if (q.steps < 1 || !q.gi || !q.w_hh || !q.out || !ctgcn_aligned16(q.gi) || !ctgcn_aligned16(q.w_hh) || (reinterpret_cast<uintptr_t>(q.out) & 7u) ||
             (q.ld_out > 0 && (q.ld_out < GRU_H || (q.ld_out & 1))) || (q.row_order == nullptr) != (q.tile_mask == nullptr) ||
             (q.row_order == nullptr) != (q.tile_base == nullptr) || (q.row_order && q.steps > 32))
             return fail(CTGCN_E_INVALID, "gru_seq_group: bad arguments of group %d", i);
@@ -5013,7 +5011,7 @@ int ctgcn_gru_layer_presplit_group_f32(int32_t groups, int64_t rows, int32_t hid
     double total = 0.0;
     for (int i = 0; i < groups; ++i) {
         const ctgcn_gru_layer_group_t &q = g[i];
-        if (q.steps < 1 || !q.planes || !q.w_ih || !q.w_hh || !q.out || (reinterpret_cast<uintptr_t>(q.planes) & 255u) || !aligned16(q.w_ih) || !aligned16(q.w_hh) ||
+        if (q.steps < 1 || !q.planes || !q.w_ih || !q.w_hh || !q.out || (reinterpret_cast<uintptr_t>(q.planes) & 255u) || !ctgcn_aligned16(q.w_ih) || !ctgcn_aligned16(q.w_hh) ||
             (reinterpret_cast<uintptr_t>(q.out) & 7u) || (q.ld_out > 0 && (q.ld_out < GRU_H || (q.ld_out & 1))) ||
             (q.row_order == nullptr) != (q.tile_mask == nullptr) || (q.row_order && q.steps > 32))
             return fail(CTGCN_E_INVALID, "gru_layer_presplit_group: bad arguments of group %d", i);
@@ -5093,7 +5091,7 @@ int ctgcn_gru_input_proj_f32(int64_t rows, int32_t d_in, int32_t hidden, const f
     if (rows < 0 || ldx < d_in) return fail(CTGCN_E_INVALID, "gru_input_proj: bad sizes");
     if (rows == 0) return CTGCN_OK;
     if (!x || !w_ih || !gi) return fail(CTGCN_E_INVALID, "gru_input_proj: null pointer");
-    if (!aligned16(x) || !aligned16(w_ih) || (ldx % 4)) return fail(CTGCN_E_INVALID, "gru_input_proj: x / w_ih must be 16-byte aligned, ldx a multiple of 4");
+    if (!ctgcn_aligned16(x) || !ctgcn_aligned16(w_ih) || (ldx % 4)) return fail(CTGCN_E_INVALID, "gru_input_proj: x / w_ih must be 16-byte aligned, ldx a multiple of 4");
     ProjArgs a{};
     a.rows = rows; a.x = x; a.ldx = ldx; a.w = w_ih; a.bias = bias; a.out = gi;
     if (steps_blocked < 0 || (steps_blocked > 0 && (split_mode != CTGCN_SPLIT_F16X2 || rows % steps_blocked)))
@@ -5121,7 +5119,7 @@ int ctgcn_gru_input_grad_f32(int64_t rows, int32_t d_in, int32_t hidden, const f
     if (rows < 0 || ldx < d_in) return fail(CTGCN_E_INVALID, "gru_input_grad: bad sizes");
     if (rows == 0) return CTGCN_OK;
     if (!d_gi || !w_ih || !d_x) return fail(CTGCN_E_INVALID, "gru_input_grad: null pointer");
-    if (!aligned16(d_gi) || !aligned16(d_x) || (ldx % 4)) return fail(CTGCN_E_INVALID, "gru_input_grad: d_gi / d_x must be 16-byte aligned, ldx a multiple of 4");
+    if (!ctgcn_aligned16(d_gi) || !ctgcn_aligned16(d_x) || (ldx % 4)) return fail(CTGCN_E_INVALID, "gru_input_grad: d_gi / d_x must be 16-byte aligned, ldx a multiple of 4");
     DxArgs a{};
     a.rows = rows; a.g = d_gi; a.w = w_ih; a.out = d_x; a.ldo = ldx;
     int dev = 0, cus = 256;
@@ -5160,7 +5158,7 @@ int ctgcn_lstm_seq_f32(int64_t rows, int32_t steps, int32_t hidden, const float 
     if (rows < 0 || steps < 1) return fail(CTGCN_E_INVALID, "lstm_seq: bad sizes");
     if (rows == 0) return CTGCN_OK;
     if (!gi || !w_hh || !out) return fail(CTGCN_E_INVALID, "lstm_seq: null pointer");
-    if (!aligned16(w_hh) || (reinterpret_cast<uintptr_t>(out) & 7u)) return fail(CTGCN_E_INVALID, "lstm_seq: w_hh must be 16-byte aligned, out 8-byte aligned");
+    if (!ctgcn_aligned16(w_hh) || (reinterpret_cast<uintptr_t>(out) & 7u)) return fail(CTGCN_E_INVALID, "lstm_seq: w_hh must be 16-byte aligned, out 8-byte aligned");
     GruArgs a{};
     a.rows = rows; a.steps = steps; a.gi = gi; a.whh = w_hh; a.bhn = nullptr; a.gamma = ln_weight; a.beta = ln_bias;
     a.eps = ln_eps; a.reduce_sum = reduce_sum ? 1 : 0; a.out = out; a.gates = gates_out; a.ldo = GRU_H;

@@ -437,15 +437,6 @@ static int check_table(const char *what, int32_t problems, int32_t d, int64_t bl
     return CTGCN_OK;
 }
 
-static int fail(int code, const char *what, const char *text)
-{
-    char buf[192];
-    snprintf(buf, sizeof(buf), "%s: %s", what, text);
-    return ctgcn_set_error_(code, buf);
-}
-
-static int can_vec4(int32_t d, const float *E, int64_t lde) { return d % 4 == 0 && lde % 4 == 0 && (reinterpret_cast<uintptr_t>(E) & 15) == 0; }
-
 extern "C" int64_t ctgcn_nc_chunks(int64_t n) { return chunks_of(n); }
 
 extern "C" int64_t ctgcn_nc_hess_parts(int64_t n, int64_t hess_max) { return hess_max < 1 ? 0 : hess_parts_of(n, hess_max); }
@@ -467,16 +458,16 @@ static int grad_impl(const char *what, int32_t problems, int32_t d, int32_t max_
 {
     int rc = check_table(what, problems, d, total_chunks, row_start, chunk_start, rows, y, model_start, model_flag, n_emb, E, lde, W, models);
     if (rc) return rc;
-    if (PAIR && !rows2) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (max_models < 1 || max_models > 0xffff * 64) return fail(CTGCN_E_INVALID, what, "bad max_models");
+    if (PAIR && !rows2) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (max_models < 1 || max_models > 0xffff * 64) return ctgcn_fail(CTGCN_E_INVALID, what, "bad max_models");
     if (models == 0) return CTGCN_OK;
-    if (!model_pos || !model_w || !loss_out || !grad_out || !workspace) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!model_pos || !model_w || !loss_out || !grad_out || !workspace) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     if (workspace_bytes < ctgcn_nc_grad_workspace_bytes(total_chunks, d, max_models))
-        return fail(CTGCN_E_WORKSPACE, what, "workspace too small");
+        return ctgcn_fail(CTGCN_E_WORKSPACE, what, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int gm = std::min((int)max_models, group_max(d));
     const int G = (max_models + gm - 1) / gm;
-    const Table tb{problems, row_start, chunk_start, rows, rows2, PAIR ? can_vec4(d, E, lde) : 0, y, model_start, model_pos, model_w, model_flag};
+    const Table tb{problems, row_start, chunk_start, rows, rows2, PAIR ? ctgcn_can_vec4(d, E, lde) : 0, y, model_start, model_pos, model_w, model_flag};
     const size_t lds = pass_lds(d, gm);
     if ((rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(nc_pass_kernel<false, PAIR>), lds, "nodecls"))) return rc;
     double *part = (double *)workspace;
@@ -524,14 +515,14 @@ static int hess_impl(const char *what, int32_t problems, int32_t d, int32_t max_
 {
     int rc = check_table(what, problems, d, total_parts, row_start, part_start, rows, y, model_start, model_flag, n_emb, E, lde, W, models);
     if (rc) return rc;
-    if (PAIR && !rows2) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (max_models < 1 || max_models > 0xffff || hess_max < 1) return fail(CTGCN_E_INVALID, what, "bad max_models or hess_max");
+    if (PAIR && !rows2) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (max_models < 1 || max_models > 0xffff || hess_max < 1) return ctgcn_fail(CTGCN_E_INVALID, what, "bad max_models or hess_max");
     if (models == 0) return CTGCN_OK;
-    if (!model_pos || !model_w || !hess_out || !workspace) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!model_pos || !model_w || !hess_out || !workspace) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     if (workspace_bytes < ctgcn_nc_hess_workspace_bytes(total_parts, d, max_models))
-        return fail(CTGCN_E_WORKSPACE, what, "workspace too small");
+        return ctgcn_fail(CTGCN_E_WORKSPACE, what, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const Table tb{problems, row_start, part_start, rows, rows2, PAIR ? can_vec4(d, E, lde) : 0, y, model_start, model_pos, model_w, model_flag};
+    const Table tb{problems, row_start, part_start, rows, rows2, PAIR ? ctgcn_can_vec4(d, E, lde) : 0, y, model_start, model_pos, model_w, model_flag};
     const int D1 = d + 1, D4 = (D1 + 3) & ~3;
     const size_t lds = sizeof(float) * ((size_t)TE * D4 + TE);
     float *part = (float *)workspace;
@@ -576,14 +567,14 @@ static int predict_impl(const char *what, int32_t problems, int32_t d, int32_t m
 {
     int rc = check_table(what, problems, d, total_chunks, row_start, chunk_start, rows, y, model_start, model_flag, n_emb, E, lde, W, models);
     if (rc) return rc;
-    if (PAIR && !rows2) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (groups < 1 || max_classes < 2) return fail(CTGCN_E_INVALID, what, "need groups >= 1 and max_classes >= 2");
+    if (PAIR && !rows2) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (groups < 1 || max_classes < 2) return ctgcn_fail(CTGCN_E_INVALID, what, "need groups >= 1 and max_classes >= 2");
     if (max_classes > group_max(d)) {
         char buf[96];
         snprintf(buf, sizeof(buf), "%d classes, at most %d at d = %d (the models of one block)", (int)max_classes, group_max(d), (int)d);
-        return fail(CTGCN_E_UNSUPPORTED, what, buf);
+        return ctgcn_fail(CTGCN_E_UNSUPPORTED, what, buf);
     }
-    if (!n_classes || !pred_out || !correct_out) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!n_classes || !pred_out || !correct_out) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     CTGCN_TRY(hipMemsetAsync(correct_out, 0, sizeof(int64_t) * problems * groups, st));
     if (models == 0) return CTGCN_OK;
@@ -591,8 +582,8 @@ static int predict_impl(const char *what, int32_t problems, int32_t d, int32_t m
     const int gm = std::min(group_max(d), groups * mpg);
     const int gpb = gm / mpg;
     const int G = (groups + gpb - 1) / gpb;
-    if (G > 0xffff) return fail(CTGCN_E_UNSUPPORTED, what, "too many C groups");
-    const Table tb{problems, row_start, chunk_start, rows, rows2, PAIR ? can_vec4(d, E, lde) : 0, y, model_start, nullptr, nullptr, model_flag};
+    if (G > 0xffff) return ctgcn_fail(CTGCN_E_UNSUPPORTED, what, "too many C groups");
+    const Table tb{problems, row_start, chunk_start, rows, rows2, PAIR ? ctgcn_can_vec4(d, E, lde) : 0, y, model_start, nullptr, nullptr, model_flag};
     const size_t lds = pass_lds(d, gm);
     if ((rc = ctgcn_opt_in_lds(reinterpret_cast<const void *>(nc_pass_kernel<true, PAIR>), lds, "nodecls"))) return rc;
     hipLaunchKernelGGL((nc_pass_kernel<true, PAIR>), dim3((unsigned)total_chunks, (unsigned)G), dim3(THREADS), lds, st, tb, (int)d, gm,

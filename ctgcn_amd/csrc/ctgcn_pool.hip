@@ -10,7 +10,7 @@
 //   batch norm  column statistics in fp64 (per-block shifted sums, merged by Chan's formula in a fixed order), the apply pass
 //               y = dropout(relu((x - mean) rstd w + b)), and a backward that recomputes the ReLU mask and the draw from x.
 //
-// Pull form as in ctgcn_gcn.hip: a group of LPR lanes owns a destination row, each lane a float4 (or a float) of it, and walks the
+// Pull form as in ctgcn_gather.h: a group of LPR lanes owns a destination row, each lane a float4 (or a float) of it, and walks the
 // row's entries in order.  Rows longer than long_threshold entries go to a block-per-piece kernel (a piece is at most
 // 4 long_threshold entries; its eight lane groups take interleaved entries and are combined in group order) and a last kernel that
 // combines the pieces in piece order and finishes the row.  No atomics: every sum has a fixed order, and the maximum breaks ties by
@@ -18,22 +18,15 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdio>
-#include <initializer_list>
 
+#include "ctgcn_gather.h"
 #include "ctgcn_rng.h"
 #include "ctgcn_try.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef int i4 __attribute__((ext_vector_type(4)));
 
-constexpr int PIECE_FACTOR = 4;        // entries of a long row's piece, in units of long_threshold (ops.GCN_PIECE_FACTOR)
-constexpr int PIECE_THREADS = 256;
-constexpr int PIECE_LANES = 32;        // lanes across the feature row in the piece kernel
-constexpr int PIECE_GROUPS = PIECE_THREADS / PIECE_LANES;
-constexpr float L2_EPS = 1e-12f;       // F.normalize's eps: the denominator is max(norm, eps)
 constexpr int MODE_SUM = 0, MODE_MAX = 1, MODE_PULL = 2;
 
 template <int VEC> __device__ __forceinline__ void ldf(const float *p, float (&x)[VEC]);
@@ -89,13 +82,6 @@ struct PoolArgs {
     float *part;            // [n_long][max_pieces][part_ld]
     int32_t *part_arg;      // MAX: the same shape
 };
-
-__host__ __device__ __forceinline__ int pieces_of(int len, int long_thresh, int max_pieces)
-{
-    const int64_t piece = (int64_t)PIECE_FACTOR * long_thresh;
-    const int64_t np = (len + piece - 1) / piece;
-    return (int)(np < 1 ? 1 : (np > max_pieces ? max_pieces : np));
-}
 
 // the candidate (x, c) against the best so far: larger wins, the lower column index among equals; c < 0 is no candidate
 __device__ __forceinline__ void better(float x, int c, float &best, int &arg)
@@ -295,10 +281,7 @@ __global__ __launch_bounds__(64) void pool_final_kernel(const PoolArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ pool conv: backward pre-pass
-constexpr int PREP_ROWS = 64;          // rows of a block: one partial column-sum vector per block
-constexpr int PREP_WAVES = 4;          // wave w takes the block's rows w, w + 4, ...; its lanes lie across the feature row
-constexpr int DB_COLS = 32, DB_SEGS = 32;
-
+// PREP_ROWS rows a block, one partial column-sum vector per block; colsum_kernel (ctgcn_gather.h) adds them in block order
 struct PrepArgs {
     int64_t n;
     int32_t d, chunks, drop;
@@ -389,25 +372,6 @@ __global__ __launch_bounds__(64 * PREP_WAVES) void pool_prep_kernel(const PrepAr
             }
             __syncthreads();
         }
-    }
-}
-
-// out[c] = sum over the blocks of part[b][c]: DB_SEGS runs of consecutive blocks, each in block order, then the runs in run order
-__global__ __launch_bounds__(DB_COLS * DB_SEGS) void pool_colsum_kernel(int64_t blocks, int32_t d, int32_t part_ld, const float *part, float *out)
-{
-    __shared__ float sm[DB_SEGS][DB_COLS];
-    const int cx = threadIdx.x % DB_COLS, seg = threadIdx.x / DB_COLS;
-    const int64_t c = (int64_t)blockIdx.x * DB_COLS + cx;
-    const int64_t per = (blocks + DB_SEGS - 1) / DB_SEGS;
-    const int64_t lo = min(blocks, seg * per), hi = min(blocks, lo + per);
-    float t = 0.f;
-    if (c < d)
-        for (int64_t b = lo; b < hi; ++b) t += part[b * part_ld + c];
-    sm[seg][cx] = t;
-    __syncthreads();
-    if (seg == 0 && c < d) {
-        for (int k = 1; k < DB_SEGS; ++k) t += sm[k][cx];
-        out[c] = t;
     }
 }
 
@@ -623,53 +587,14 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const BnArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int fail(int code, const char *what, const char *text)
-{
-    char buf[224];
-    snprintf(buf, sizeof(buf), "%s: %s", what, text);
-    return ctgcn_set_error_(code, buf);
-}
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// p as [.][ld] rows, or a vector with ld 0; a null p is an operand the call does not have
-struct Operand {
-    const void *p;
-    int64_t ld;
-};
-
-// float4 rows: d and every leading dimension a multiple of 4, every base 16-byte aligned
-bool float4_rows(int32_t d, std::initializer_list<Operand> operands)
-{
-    if (d % 4) return false;
-    for (const Operand &o : operands)
-        if (o.p && (o.ld % 4 || !aligned16(o.p))) return false;
-    return true;
-}
-
-bool bad_p(double p) { return !(p >= 0.0 && p < 1.0); }
-
 template <int VEC, int MODE>
 int launch(PoolArgs a, hipStream_t st)
 {
     a.chunks = a.d / VEC;                                         // VEC 4 only when d % 4 == 0
-    const int lpr = a.chunks <= 4 ? 4 : a.chunks <= 8 ? 8 : a.chunks <= 16 ? 16 : a.chunks <= 32 ? 32 : 64;
-    const dim3 grid((unsigned)((a.n + 256 / lpr - 1) / (256 / lpr)));
-    switch (lpr) {
-    case 4: hipLaunchKernelGGL((pool_row_kernel<VEC, 4, MODE>), grid, dim3(256), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((pool_row_kernel<VEC, 8, MODE>), grid, dim3(256), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((pool_row_kernel<VEC, 16, MODE>), grid, dim3(256), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((pool_row_kernel<VEC, 32, MODE>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((pool_row_kernel<VEC, 64, MODE>), grid, dim3(256), 0, st, a); break;
-    }
-    CTGCN_TRY(hipGetLastError());
-    if (a.n_long > 0) {
-        hipLaunchKernelGGL((pool_piece_kernel<VEC, MODE>), dim3((unsigned)a.max_pieces, (unsigned)a.n_long), dim3(PIECE_THREADS), 0, st, a);
-        CTGCN_TRY(hipGetLastError());
-        hipLaunchKernelGGL(pool_final_kernel<MODE>, dim3((unsigned)a.n_long), dim3(64), 0, st, a);
-        CTGCN_TRY(hipGetLastError());
-    }
-    return CTGCN_OK;
+    return launch_rows(
+        a, [&](auto lpr, dim3 grid) { hipLaunchKernelGGL((pool_row_kernel<VEC, decltype(lpr)::value, MODE>), grid, dim3(256), 0, st, a); },
+        [&](dim3 grid) { hipLaunchKernelGGL((pool_piece_kernel<VEC, MODE>), grid, dim3(PIECE_THREADS), 0, st, a); },
+        [&](dim3 grid) { hipLaunchKernelGGL(pool_final_kernel<MODE>, grid, dim3(64), 0, st, a); });
 }
 
 template <int MODE>
@@ -683,27 +608,17 @@ int dispatch(const PoolArgs &a, bool v4, void *stream)
 int set_common(PoolArgs &a, const char *what, int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const int32_t *long_rows,
                int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes, int words)
 {
-    if (n < 0 || n > INT32_MAX || d < 1) return fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
-    if (n_long < 0 || n_long > n) return fail(CTGCN_E_INVALID, what, "n_long outside [0, n]");
+    if (n < 0 || n > INT32_MAX || d < 1) return ctgcn_fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
+    if (n_long < 0 || n_long > n) return ctgcn_fail(CTGCN_E_INVALID, what, "n_long outside [0, n]");
     if (n == 0) return CTGCN_OK;
-    if (!row_ptr && n_long > 0) return fail(CTGCN_E_INVALID, what, "long rows without a matrix");
-    if (row_ptr && !col) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!row_ptr && n_long > 0) return ctgcn_fail(CTGCN_E_INVALID, what, "long rows without a matrix");
+    if (row_ptr && !col) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     a.n = n; a.d = d; a.row_ptr = row_ptr; a.col = col;
-    a.long_rows = long_rows; a.n_long = n_long; a.long_thresh = long_threshold;
     a.part_ld = (d + 3) & ~3;
-    if (n_long > 0) {
-        if (!long_rows) return fail(CTGCN_E_INVALID, what, "n_long > 0 without long_rows");
-        if (long_threshold < 1 || long_threshold > INT32_MAX / PIECE_FACTOR) return fail(CTGCN_E_INVALID, what, "long_threshold outside [1, 2^29)");
-        if (n_long > 65535) return fail(CTGCN_E_UNSUPPORTED, what, "more than 65535 long rows: raise long_threshold");
-        const size_t one = (size_t)n_long * a.part_ld * sizeof(float) * words;
-        if (!workspace || !aligned16(workspace) || workspace_bytes < one)
-            return fail(CTGCN_E_WORKSPACE, what,
-                        "long rows need a 16-byte aligned workspace of at least n_long * round_up(d, 4) * 4 bytes (8 for pool_max_fwd), one piece per row");
-        const size_t mp = workspace_bytes / one;
-        a.max_pieces = (int32_t)(mp > 4096 ? 4096 : mp);
-        a.part = (float *)workspace;
-        a.part_arg = words == 2 ? (int32_t *)workspace + (size_t)n_long * a.max_pieces * a.part_ld : nullptr;
-    }
+    if (int rc = set_long_rows(a, what, long_rows, n_long, long_threshold, (size_t)a.part_ld * words, workspace, workspace_bytes,
+                               "long rows need a 16-byte aligned workspace of at least n_long * round_up(d, 4) * 4 bytes (8 for pool_max_fwd), one piece per row"))
+        return rc;
+    if (n_long > 0 && words == 2) a.part_arg = (int32_t *)workspace + (size_t)n_long * a.max_pieces * a.part_ld;
     return CTGCN_OK;
 }
 
@@ -712,12 +627,12 @@ int64_t prep_blocks(int64_t n) { return (n + PREP_ROWS - 1) / PREP_ROWS; }
 int check_bn(const char *what, int64_t n, int32_t d, const float *x, int64_t ldx, const float *mean, const float *rstd, const float *w,
              const float *b, int32_t relu, double p)
 {
-    if (n < 0 || n > INT32_MAX || d < 1) return fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
-    if (relu != 0 && relu != 1) return fail(CTGCN_E_INVALID, what, "relu must be 0 or 1");
-    if (bad_p(p)) return fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
+    if (n < 0 || n > INT32_MAX || d < 1) return ctgcn_fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
+    if (relu != 0 && relu != 1) return ctgcn_fail(CTGCN_E_INVALID, what, "relu must be 0 or 1");
+    if (bad_p(p)) return ctgcn_fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
     if (n == 0) return CTGCN_OK;
-    if (!x || !mean || !rstd || !w || !b) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (ldx < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (!x || !mean || !rstd || !w || !b) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (ldx < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     return CTGCN_OK;
 }
 
@@ -738,13 +653,13 @@ extern "C" int ctgcn_pool_conv_fwd_f32(int64_t n, int32_t d, const int32_t *row_
 {
     const char *what = "pool_conv_fwd";
     PoolArgs a{};
-    if (epi != 0 && epi != 1) return fail(CTGCN_E_INVALID, what, "epi must be 0 (none) or 1 (ReLU, L2 row normalisation, dropout)");
-    if (bad_p(p)) return fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
+    if (epi != 0 && epi != 1) return ctgcn_fail(CTGCN_E_INVALID, what, "epi must be 0 (none) or 1 (ReLU, L2 row normalisation, dropout)");
+    if (bad_p(p)) return ctgcn_fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
     const bool drop = epi == 1 && p > 0.0;
-    if ((row_ptr && lds < d) || ldy < d || (T && ldt < d) || (drop && Ysave && ldsave < d)) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if ((row_ptr && lds < d) || ldy < d || (T && ldt < d) || (drop && Ysave && ldsave < d)) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     if (int rc = set_common(a, what, n, d, row_ptr, col, long_rows, n_long, long_threshold, workspace, workspace_bytes, 1)) return rc;
     if (n == 0) return CTGCN_OK;
-    if (!Y || (row_ptr && (!S || !val)) || (epi == 1 && !norm)) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!Y || (row_ptr && (!S || !val)) || (epi == 1 && !norm)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     a.val = val; a.src = S; a.ldsrc = lds; a.self = T; a.ldself = ldt; a.self_scale = self_scale; a.bias = bias; a.out = Y; a.ldout = ldy;
     a.epi = epi; a.drop = drop; a.norm = norm; a.ysave = drop ? Ysave : nullptr; a.ldsave = ldsave;
     a.p = p; a.scale = 1.0f / (1.0f - (float)p); a.key = key;
@@ -762,13 +677,13 @@ extern "C" int ctgcn_pool_conv_prep_f32(int64_t n, int32_t d, const float *dY, i
                                         void *stream)
 {
     const char *what = "pool_conv_prep";
-    if (n < 0 || n > INT32_MAX || d < 1) return fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
-    if (bad_p(p)) return fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
+    if (n < 0 || n > INT32_MAX || d < 1) return ctgcn_fail(CTGCN_E_INVALID, what, "need 0 <= n < 2^31 and d >= 1");
+    if (bad_p(p)) return ctgcn_fail(CTGCN_E_INVALID, what, "dropout p outside [0, 1)");
     if (n == 0) return CTGCN_OK;
-    if (!dY || !Y || !G || !norm) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (lddy < d || ldy < d || ldg < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
-    if (db && (!workspace || !aligned16(workspace) || workspace_bytes < ctgcn_pool_prep_workspace_bytes(n, d)))
-        return fail(CTGCN_E_WORKSPACE, what, "a bias gradient needs a 16-byte aligned workspace of ctgcn_pool_prep_workspace_bytes() bytes");
+    if (!dY || !Y || !G || !norm) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (lddy < d || ldy < d || ldg < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (db && (!workspace || !ctgcn_aligned16(workspace) || workspace_bytes < ctgcn_pool_prep_workspace_bytes(n, d)))
+        return ctgcn_fail(CTGCN_E_WORKSPACE, what, "a bias gradient needs a 16-byte aligned workspace of ctgcn_pool_prep_workspace_bytes() bytes");
     PrepArgs a{};
     a.n = n; a.d = d; a.drop = p > 0.0; a.dY = dY; a.lddy = lddy; a.Y = Y; a.ldy = ldy; a.norm = norm; a.p = p;
     a.scale = 1.0f / (1.0f - (float)p); a.key = key; a.G = G; a.ldg = ldg; a.part = db ? (float *)workspace : nullptr; a.part_ld = (d + 3) & ~3;
@@ -780,7 +695,7 @@ extern "C" int ctgcn_pool_conv_prep_f32(int64_t n, int32_t d, const float *dY, i
     else hipLaunchKernelGGL(pool_prep_kernel<1>, dim3((unsigned)blocks), dim3(64 * PREP_WAVES), 0, st, a);
     CTGCN_TRY(hipGetLastError());
     if (db) {
-        hipLaunchKernelGGL(pool_colsum_kernel, dim3((unsigned)((d + DB_COLS - 1) / DB_COLS)), dim3(DB_COLS * DB_SEGS), 0, st, blocks, d, a.part_ld,
+        hipLaunchKernelGGL((colsum_kernel<DB_COLS, DB_SEGS>), dim3((unsigned)((d + DB_COLS - 1) / DB_COLS)), dim3(DB_COLS * DB_SEGS), 0, st, blocks, d, a.part_ld,
                            (const float *)a.part, db);
         CTGCN_TRY(hipGetLastError());
     }
@@ -793,11 +708,11 @@ extern "C" int ctgcn_pool_max_fwd_f32(int64_t n, int32_t d, const int32_t *row_p
 {
     const char *what = "pool_max_fwd";
     PoolArgs a{};
-    if (lds < d || ldy < d || ldarg < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
-    if (n > 0 && !row_ptr) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (lds < d || ldy < d || ldarg < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (n > 0 && !row_ptr) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     if (int rc = set_common(a, what, n, d, row_ptr, col, long_rows, n_long, long_threshold, workspace, workspace_bytes, 2)) return rc;
     if (n == 0) return CTGCN_OK;
-    if (!S || !Y || !arg) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!S || !Y || !arg) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     a.src = S; a.ldsrc = lds; a.out = Y; a.ldout = ldy; a.argout = arg; a.ldargout = ldarg;
     return dispatch<MODE_MAX>(a, float4_rows(d, {{S, lds}, {Y, ldy}, {arg, ldarg}}), stream);
 }
@@ -808,11 +723,11 @@ extern "C" int ctgcn_pool_max_bwd_f32(int64_t n, int32_t d, const int32_t *row_p
 {
     const char *what = "pool_max_bwd";
     PoolArgs a{};
-    if (lddy < d || ldds < d || ldarg < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
-    if (n > 0 && !row_ptr) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (lddy < d || ldds < d || ldarg < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (n > 0 && !row_ptr) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     if (int rc = set_common(a, what, n, d, row_ptr, col, long_rows, n_long, long_threshold, workspace, workspace_bytes, 1)) return rc;
     if (n == 0) return CTGCN_OK;
-    if (!dY || !dS || !arg) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!dY || !dS || !arg) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     a.src = dY; a.ldsrc = lddy; a.argin = arg; a.ldargin = ldarg; a.out = dS; a.ldout = ldds;
     return dispatch<MODE_PULL>(a, float4_rows(d, {{dY, lddy}, {dS, ldds}, {arg, ldarg}}), stream);
 }
@@ -829,14 +744,14 @@ extern "C" int ctgcn_bn_stats_f32(int64_t n, int32_t d, const float *x, int64_t 
                                   void *workspace, size_t workspace_bytes, void *stream)
 {
     const char *what = "bn_stats";
-    if (n < 1 || n > INT32_MAX || d < 1) return fail(CTGCN_E_INVALID, what, "need 1 <= n < 2^31 and d >= 1");
-    if (!(eps >= 0.0)) return fail(CTGCN_E_INVALID, what, "eps must be >= 0");
-    if (!x || !mean || !var || !rstd) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (ldx < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (n < 1 || n > INT32_MAX || d < 1) return ctgcn_fail(CTGCN_E_INVALID, what, "need 1 <= n < 2^31 and d >= 1");
+    if (!(eps >= 0.0)) return ctgcn_fail(CTGCN_E_INVALID, what, "eps must be >= 0");
+    if (!x || !mean || !var || !rstd) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (ldx < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7) || workspace_bytes < ctgcn_bn_stats_workspace_bytes(n, d))
-        return fail(CTGCN_E_WORKSPACE, what, "workspace must be 8-byte aligned and hold ctgcn_bn_stats_workspace_bytes() bytes");
+        return ctgcn_fail(CTGCN_E_WORKSPACE, what, "workspace must be 8-byte aligned and hold ctgcn_bn_stats_workspace_bytes() bytes");
     const int64_t blocks = (n + BN_ROWS - 1) / BN_ROWS;
-    if (blocks > 65535) return fail(CTGCN_E_UNSUPPORTED, what, "more than 65535 * 128 rows");
+    if (blocks > 65535) return ctgcn_fail(CTGCN_E_UNSUPPORTED, what, "more than 65535 * 128 rows");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)((d + BN_COLS - 1) / BN_COLS), (unsigned)blocks), dim3(BN_COLS * 4), 0, st, n, d, x, ldx,
                        (double *)workspace);
@@ -853,15 +768,15 @@ extern "C" int ctgcn_bn_apply_f32(int64_t n, int32_t d, const float *x, int64_t 
     const char *what = "bn_apply";
     if (int rc = check_bn(what, n, d, x, ldx, mean, rstd, weight, bias, relu, p)) return rc;
     if (n == 0) return CTGCN_OK;
-    if (!y) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (ldy < d) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (!y) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (ldy < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     BnArgs a{};
     set_bn(a, n, d, x, ldx, mean, rstd, weight, bias, relu, p, key);
     a.y = y; a.ldy = ldy;
     const bool v4 = float4_rows(d, {{x, ldx}, {y, ldy}, {mean, 0}, {rstd, 0}, {weight, 0}, {bias, 0}});
     a.chunks = v4 ? d / 4 : d;
     const int64_t blocks = (n * a.chunks + 255) / 256;
-    if (blocks > INT32_MAX) return fail(CTGCN_E_UNSUPPORTED, what, "more than 2^39 elements");
+    if (blocks > INT32_MAX) return ctgcn_fail(CTGCN_E_UNSUPPORTED, what, "more than 2^39 elements");
     hipStream_t st = (hipStream_t)stream;
     if (v4) hipLaunchKernelGGL(bn_apply_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(bn_apply_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, a);
@@ -878,27 +793,27 @@ extern "C" int ctgcn_bn_bwd_f32(int64_t n, int32_t d, const float *x, int64_t ld
 {
     const char *what = "bn_bwd";
     if (int rc = check_bn(what, n, d, x, ldx, mean, rstd, weight, bias, relu, p)) return rc;
-    if (batch_stats != 0 && batch_stats != 1) return fail(CTGCN_E_INVALID, what, "batch_stats must be 0 or 1");
+    if (batch_stats != 0 && batch_stats != 1) return ctgcn_fail(CTGCN_E_INVALID, what, "batch_stats must be 0 or 1");
     if (n == 0) return CTGCN_OK;
-    if (!dy || !dw || !db) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (lddy < d || (dx && lddx < d)) return fail(CTGCN_E_INVALID, what, "leading dimension below d");
-    if (!workspace || !aligned16(workspace) || workspace_bytes < ctgcn_bn_bwd_workspace_bytes(n, d))
-        return fail(CTGCN_E_WORKSPACE, what, "workspace must be 16-byte aligned and hold ctgcn_bn_bwd_workspace_bytes() bytes");
+    if (!dy || !dw || !db) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (lddy < d || (dx && lddx < d)) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (!workspace || !ctgcn_aligned16(workspace) || workspace_bytes < ctgcn_bn_bwd_workspace_bytes(n, d))
+        return ctgcn_fail(CTGCN_E_WORKSPACE, what, "workspace must be 16-byte aligned and hold ctgcn_bn_bwd_workspace_bytes() bytes");
     BnArgs a{};
     set_bn(a, n, d, x, ldx, mean, rstd, weight, bias, relu, p, key);
     a.dy = dy; a.lddy = lddy; a.dx = dx; a.lddx = lddx; a.dw = dw; a.db = db; a.inv_n = batch_stats ? 1.0f / (float)n : 0.f;
     a.part = (float *)workspace; a.part_ld = (d + 3) & ~3; a.blocks = prep_blocks(n);
     const bool v4 = float4_rows(d, {{x, ldx}, {dy, lddy}, {dx, lddx}, {mean, 0}, {rstd, 0}, {weight, 0}, {bias, 0}, {dw, 0}, {db, 0}});
     a.chunks = v4 ? d / 4 : d;
-    if ((n * a.chunks + 255) / 256 > INT32_MAX) return fail(CTGCN_E_UNSUPPORTED, what, "more than 2^39 elements");
+    if ((n * a.chunks + 255) / 256 > INT32_MAX) return ctgcn_fail(CTGCN_E_UNSUPPORTED, what, "more than 2^39 elements");
     hipStream_t st = (hipStream_t)stream;
     if (v4) hipLaunchKernelGGL(bn_bwd_reduce_kernel<4>, dim3((unsigned)a.blocks), dim3(64 * PREP_WAVES), 0, st, a);
     else hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3((unsigned)a.blocks), dim3(64 * PREP_WAVES), 0, st, a);
     CTGCN_TRY(hipGetLastError());
     const dim3 cgrid((unsigned)((d + DB_COLS - 1) / DB_COLS));
-    hipLaunchKernelGGL(pool_colsum_kernel, cgrid, dim3(DB_COLS * DB_SEGS), 0, st, a.blocks, d, a.part_ld, (const float *)a.part, db);
+    hipLaunchKernelGGL((colsum_kernel<DB_COLS, DB_SEGS>), cgrid, dim3(DB_COLS * DB_SEGS), 0, st, a.blocks, d, a.part_ld, (const float *)a.part, db);
     CTGCN_TRY(hipGetLastError());
-    hipLaunchKernelGGL(pool_colsum_kernel, cgrid, dim3(DB_COLS * DB_SEGS), 0, st, a.blocks, d, a.part_ld,
+    hipLaunchKernelGGL((colsum_kernel<DB_COLS, DB_SEGS>), cgrid, dim3(DB_COLS * DB_SEGS), 0, st, a.blocks, d, a.part_ld,
                        (const float *)a.part + a.blocks * a.part_ld, dw);
     CTGCN_TRY(hipGetLastError());
     if (!dx) return CTGCN_OK;

@@ -422,21 +422,12 @@ __global__ __launch_bounds__(THREADS) void cls_hub_sum_kernel(int d, int64_t n_h
     dE[v * ldde + col] = (float)s;
 }
 
-int fail(int code, const char *what, const char *text)
-{
-    char buf[192];
-    snprintf(buf, sizeof(buf), "%s: %s", what, text);
-    return ctgcn_set_error_(code, buf);
-}
-
-int can_vec4(int32_t d, const float *E, int64_t lde) { return d % 4 == 0 && lde % 4 == 0 && (reinterpret_cast<uintptr_t>(E) & 15) == 0; }
-
 // sizes shared by the three entry points: mode, d, and n_class for the modes with a head
 int check_sizes(const char *what, int32_t mode, int64_t items, int32_t d, int32_t n_class)
 {
     char buf[192];
-    if (mode != NODE && mode != HADAMARD && mode != DOT) return fail(CTGCN_E_INVALID, what, "mode must be CTGCN_CLS_NODE, _HADAMARD or _DOT");
-    if (items < 1) return fail(CTGCN_E_INVALID, what, "need items >= 1");
+    if (mode != NODE && mode != HADAMARD && mode != DOT) return ctgcn_fail(CTGCN_E_INVALID, what, "mode must be CTGCN_CLS_NODE, _HADAMARD or _DOT");
+    if (items < 1) return ctgcn_fail(CTGCN_E_INVALID, what, "need items >= 1");
     if (d < 1 || d > MAXD) {
         snprintf(buf, sizeof(buf), "%s: d = %d outside [1, %d]", what, d, MAXD);
         return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, buf);
@@ -457,10 +448,10 @@ extern "C" int64_t ctgcn_cls_pull_piece(void) { return PIECE; }
 extern "C" int ctgcn_cls_check_items(int32_t mode, int64_t items, const int64_t *a, const int64_t *b, int64_t n_nodes, void *stream)
 {
     const char *what = "cls_check_items";
-    if (mode != NODE && mode != HADAMARD && mode != DOT) return fail(CTGCN_E_INVALID, what, "mode must be CTGCN_CLS_NODE, _HADAMARD or _DOT");
-    if (items < 0 || n_nodes < 1) return fail(CTGCN_E_INVALID, what, "need items >= 0 and n_nodes >= 1");
+    if (mode != NODE && mode != HADAMARD && mode != DOT) return ctgcn_fail(CTGCN_E_INVALID, what, "mode must be CTGCN_CLS_NODE, _HADAMARD or _DOT");
+    if (items < 0 || n_nodes < 1) return ctgcn_fail(CTGCN_E_INVALID, what, "need items >= 0 and n_nodes >= 1");
     if (items == 0) return CTGCN_OK;
-    if (!a || (mode != NODE && !b)) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!a || (mode != NODE && !b)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     std::vector<int64_t> host((size_t)items);
     for (const int64_t *src : {a, mode != NODE ? b : (const int64_t *)nullptr}) {
@@ -484,9 +475,9 @@ extern "C" int ctgcn_cls_head_fwd_f32(int32_t mode, int32_t act, int64_t items, 
     const char *what = "cls_head_fwd";
     int rc = check_sizes(what, mode, items, d, n_class);
     if (rc) return rc;
-    if (n_nodes < 1 || lde < d) return fail(CTGCN_E_INVALID, what, "need n_nodes >= 1 and lde >= d");
-    if (act != 0 && act != 1) return fail(CTGCN_E_INVALID, what, "act must be 0 (identity) or 1 (SELU)");
-    if (!a || (mode != NODE && !b) || !E || !out || (mode != DOT && !W)) return fail(CTGCN_E_INVALID, what, "null pointer");
+    if (n_nodes < 1 || lde < d) return ctgcn_fail(CTGCN_E_INVALID, what, "need n_nodes >= 1 and lde >= d");
+    if (act != 0 && act != 1) return ctgcn_fail(CTGCN_E_INVALID, what, "act must be 0 (identity) or 1 (SELU)");
+    if (!a || (mode != NODE && !b) || !E || !out || (mode != DOT && !W)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (mode == DOT) {
         hipLaunchKernelGGL(cls_dot_fwd_kernel, dim3(grid_of((items + WAVES - 1) / WAVES)), dim3(THREADS), 0, st, (int)d, items, a, b, n_nodes, E,
@@ -494,7 +485,7 @@ extern "C" int ctgcn_cls_head_fwd_f32(int32_t mode, int32_t act, int64_t items, 
         CTGCN_TRY(hipGetLastError());
         return CTGCN_OK;
     }
-    const int DW = wstride(d), vec4 = can_vec4(d, E, lde);
+    const int DW = wstride(d), vec4 = ctgcn_can_vec4(d, E, lde);
     const size_t lds = sizeof(float) * ((size_t)TE * DW + (size_t)n_class * DW);
     const dim3 grid(grid_of((items + TE - 1) / TE));
     if (mode == NODE) {
@@ -523,9 +514,9 @@ extern "C" int ctgcn_cls_loss_f32(int32_t mode, int32_t act, int64_t items, int3
     const char *what = "cls_loss";
     int rc = check_sizes(what, mode, items, 1, n_class);
     if (rc) return rc;
-    if (act != 0 && act != 1) return fail(CTGCN_E_INVALID, what, "act must be 0 (identity) or 1 (SELU)");
-    if (!logits || !labels || !loss_out || !correct_out || !workspace) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (workspace_bytes < ctgcn_cls_loss_workspace_bytes(items)) return fail(CTGCN_E_WORKSPACE, what, "workspace too small");
+    if (act != 0 && act != 1) return ctgcn_fail(CTGCN_E_INVALID, what, "act must be 0 (identity) or 1 (SELU)");
+    if (!logits || !labels || !loss_out || !correct_out || !workspace) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (workspace_bytes < ctgcn_cls_loss_workspace_bytes(items)) return ctgcn_fail(CTGCN_E_WORKSPACE, what, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int64_t blocks = loss_blocks(items);
     double *part_loss = (double *)workspace;
@@ -555,18 +546,18 @@ extern "C" int ctgcn_cls_head_bwd_f32(int32_t mode, int64_t items, int32_t d, in
     int rc = check_sizes(what, mode, items, d, n_class);
     if (rc) return rc;
     const int C = mode == DOT ? 1 : n_class;
-    if (n_nodes < 1 || lde < d) return fail(CTGCN_E_INVALID, what, "need n_nodes >= 1 and lde >= d");
-    if (!a || (mode != NODE && !b) || !E || !dlogits || (mode != DOT && !W) || !workspace) return fail(CTGCN_E_INVALID, what, "null pointer");
-    if (mode == DOT && (dW || db)) return fail(CTGCN_E_INVALID, what, "CTGCN_CLS_DOT has no head: dW and db must be null");
-    if (db && !dW) return fail(CTGCN_E_INVALID, what, "db needs dW");
-    if (workspace_bytes < ctgcn_cls_head_bwd_workspace_bytes(items, d, C, hub_pieces)) return fail(CTGCN_E_WORKSPACE, what, "workspace too small");
+    if (n_nodes < 1 || lde < d) return ctgcn_fail(CTGCN_E_INVALID, what, "need n_nodes >= 1 and lde >= d");
+    if (!a || (mode != NODE && !b) || !E || !dlogits || (mode != DOT && !W) || !workspace) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (mode == DOT && (dW || db)) return ctgcn_fail(CTGCN_E_INVALID, what, "CTGCN_CLS_DOT has no head: dW and db must be null");
+    if (db && !dW) return ctgcn_fail(CTGCN_E_INVALID, what, "db needs dW");
+    if (workspace_bytes < ctgcn_cls_head_bwd_workspace_bytes(items, d, C, hub_pieces)) return ctgcn_fail(CTGCN_E_WORKSPACE, what, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     double *hub_part = (double *)workspace;
     double *dw_part = hub_part + (size_t)hub_pieces * d;
     if (dE) {
-        if (n_pieces < n_nodes || n_hubs < 0 || hub_pieces < 0 || ldde < d) return fail(CTGCN_E_INVALID, what, "bad piece table sizes or ldde < d");
+        if (n_pieces < n_nodes || n_hubs < 0 || hub_pieces < 0 || ldde < d) return ctgcn_fail(CTGCN_E_INVALID, what, "bad piece table sizes or ldde < d");
         if (!piece_ptr || !piece_node || !piece_slot || !inc_item || (mode != NODE && !inc_other) || (n_hubs > 0 && (!hub_node || !hub_slot_ptr)))
-            return fail(CTGCN_E_INVALID, what, "null pointer");
+            return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
         const size_t lds = mode == DOT ? 0 : sizeof(float) * (size_t)C * d;
         const dim3 grid(grid_of((n_pieces + WAVES - 1) / WAVES));
 #define CTGCN_CLS_PULL(M)                                                                                                                       \
@@ -581,7 +572,7 @@ extern "C" int ctgcn_cls_head_bwd_f32(int32_t mode, int64_t items, int32_t d, in
                                n_nodes, hub_node, hub_slot_ptr, (const double *)hub_part, dE, ldde);
     }
     if (dW) {
-        const int DW = wstride(d), vec4 = can_vec4(d, E, lde);
+        const int DW = wstride(d), vec4 = ctgcn_can_vec4(d, E, lde);
         const int64_t blocks = dw_blocks(items);
         const size_t lds = sizeof(float) * ((size_t)TE * DW + (size_t)TE * C);
         if (mode == NODE) {

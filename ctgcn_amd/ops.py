@@ -1930,7 +1930,7 @@ def cls_loss_autograd(logits, labels, dot=False):
 
 # ------------------------------------------------------------------------- GCN step of the EvolveGCN baseline (ctgcn_gcn.hip)
 GCN_ACT_NONE, GCN_ACT_RRELU = 0, 1
-GCN_PIECE_FACTOR = 4                    # a long row's piece holds 4 x long_threshold entries (ctgcn_gcn.hip)
+GCN_PIECE_FACTOR = 4                    # a long row's piece holds 4 x long_threshold entries (PIECE_FACTOR in ctgcn_gather.h)
 
 
 def gcn_normalize(row_ptr, col, val, row_norm=False):
