@@ -10,13 +10,15 @@ from .core_adj import CoreAdj  # noqa: F401
 from .layers import CoreDiffusion, MLP  # noqa: F401
 from .models import CDN, CGCN, CTGCN, EdgeClassifier, InnerProduct, MLPClassifier  # noqa: F401
 from .helper import DataLoader  # noqa: F401
-from .metrics import ClassificationLoss, NegativeSamplingLoss, ReconstructionLoss, StructureClassificationLoss  # noqa: F401
+from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLoss, StructureClassificationLoss, VAEClassificationLoss,  # noqa: F401
+                      VAELoss)
 from .embedding import SupervisedEmbedding, UnsupervisedEmbedding  # noqa: F401
 from .baseline import (GAT, GCN, GCRN, GIN, PGNN, SAGE, Aggregator, EvolveGCN, GraphConvolution, Nonlinear, PGNN_layer,  # noqa: F401
-                       SAGE_Layer, SpGraphAttentionLayer)
+                       SAGE_Layer, SpGraphAttentionLayer, VGRNN, GCNConv, InnerProductDecoder, graph_gru_gcn)
 from .evaluation import DataGenerator, LinkPredictor, aggregate_results, evaluate, evaluate_window, link_prediction  # noqa: F401
 
 __all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoader", "NegativeSamplingLoss", "ReconstructionLoss",
            "UnsupervisedEmbedding", "SupervisedEmbedding", "MLPClassifier", "InnerProduct", "EdgeClassifier", "ClassificationLoss",
            "StructureClassificationLoss", "DataGenerator", "LinkPredictor", "aggregate_results", "evaluate", "evaluate_window", "link_prediction", "EvolveGCN",
-           "GCN", "GraphConvolution", "GCRN", "GAT", "SpGraphAttentionLayer", "GIN", "SAGE", "SAGE_Layer", "Aggregator", "PGNN", "PGNN_layer", "Nonlinear"]
+           "GCN", "GraphConvolution", "GCRN", "GAT", "SpGraphAttentionLayer", "GIN", "SAGE", "SAGE_Layer", "Aggregator", "PGNN", "PGNN_layer", "Nonlinear",
+           "VGRNN", "GCNConv", "graph_gru_gcn", "InnerProductDecoder", "VAELoss", "VAEClassificationLoss"]

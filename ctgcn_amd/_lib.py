@@ -197,6 +197,16 @@ SIGNATURES = {
                                             _i64, _vp, _i64, _vp, _sz, _vp]),
     "ctgcn_pgnn_table_grad_workspace_bytes": (_sz, [_i64]),
     "ctgcn_pgnn_table_grad_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_vae_nll_tile": (_i32, []),
+    "ctgcn_vae_nll_workspace_bytes": (_sz, [_i64, _i64]),
+    "ctgcn_vae_nll_dense_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ctgcn_vae_nll_entries_f32": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "ctgcn_vgrnn_bwd_prep_f32": (_int, [_i32, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                        _vp, _sz, _vp]),
+    "ctgcn_ggru_gates_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_ggru_blend_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _sz,
+                                        _vp]),
+    "ctgcn_vgrnn_heads_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

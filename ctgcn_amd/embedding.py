@@ -1,5 +1,5 @@
 """UnsupervisedEmbedding: the reference's unsupervised trainer (reference embedding.py:13-89, 293-368) for CTGCN-C/-S, CGCN-C/-S and the
-EvolveGCN, GCRN, GAT, GIN, SAGE and PGNN baselines (single-output models: trained like the -C models).
+EvolveGCN, GCRN, GAT, GIN, SAGE and PGNN baselines (single-output models: trained like the -C models), and for the VGRNN baseline.
 
 The reference runs, per epoch, one full-graph forward + loss(batch) + backward for each of the ceil(N / batch_size) batches of a
 shuffled node order and steps Adam once after the last batch (gradient accumulation).  The weights do not change inside an epoch
@@ -14,6 +14,11 @@ reference's get_model_res does.  The fused epoch makes one forward per epoch and
 them per batch, as the reference does.  Under torch.manual_seed the fused paths repeat a run bit for bit; the unfused paths gather rows
 with torch's indexing, whose backward adds with float atomics, and repeat bit for bit under torch.use_deterministic_algorithms(True).
 
+A VGRNN takes (x_list, edge_list, hx) and trains with metrics.VAELoss on its own loss data plus adj_list (U-own).  Its loss covers
+all nodes, so a batch is a full forward and the full loss: the reference's loop is run as it stands, hx carried from batch to batch
+(detached on entry by the model) and Adam stepped once per epoch.  fused selects the model's kernel path or its composed stock-torch
+path.
+
 SupervisedEmbedding is the reference's supervised trainer (embedding.py:93-290) for the learning types S-node, S-edge, S-link-st
 and S-link-dy on the same models; its classifier head and loss run the kernels of ctgcn_supervised.hip.
 """
@@ -25,18 +30,19 @@ import torch
 
 from ._lib import CtgcnHipError
 from .export import save_embedding
-from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLoss, StructureClassificationLoss, _seed_base,
-                      epoch_batch_seed)
+from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLoss, StructureClassificationLoss, VAEClassificationLoss,
+                      VAELoss, _seed_base, epoch_batch_seed)
 
 _S_MODELS = ('CGCN-S', 'CTGCN-S')
-_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT', 'GIN', 'SAGE', 'PGNN')      # the baselines: single-output, trained like the -C models
+_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT', 'GIN', 'SAGE', 'PGNN', 'VGRNN')      # the baselines: single-output, trained like the -C models
 
 
 def _check_own_baseline(trainer, model, name):
-    """GIN, SAGE and PGNN are trained as this package's own modules, whose passes run in ctgcn_pool.hip and ctgcn_pgnn.hip.  Another module
+    """GIN, SAGE, PGNN and VGRNN are trained as this package's own modules, whose passes run in ctgcn_pool.hip, ctgcn_pgnn.hip and
+    ctgcn_vgrnn.hip.  Another module
     that carries the name (the reference's classes with their dense masks and Python loops, or a model relabelled by hand) has no such
     path and is refused, not run through whatever forward it happens to have."""
-    if name in ('GIN', 'SAGE', 'PGNN'):
+    if name in ('GIN', 'SAGE', 'PGNN', 'VGRNN'):
         from . import baseline
         cls = getattr(baseline, name)
         if not isinstance(model, cls):
@@ -51,6 +57,11 @@ def model_forward(model, x_list, adj_list, node_dist_list, node_num, device):
     from .baseline.pgnn import preselect_anchor
     dists_max, dists_argmax = preselect_anchor(node_num, node_dist_list, device, node_ids=bool(getattr(model, 'anchor_node_ids', False)))
     return model(x_list, dists_max, dists_argmax)
+
+
+def _check_edge_list(name, edge_list, steps):
+    if name == 'VGRNN' and (edge_list is None or len(edge_list) != steps):
+        raise ValueError("a VGRNN needs edge_list: one [2, E] index tensor (or prepared adjacency) per snapshot")
 
 
 def _check_node_dist(name, node_dist_list):
@@ -120,7 +131,7 @@ class UnsupervisedEmbedding(object):
         if name not in _SUPPORTED:
             raise NotImplementedError("UnsupervisedEmbedding covers %s, not %r" % (', '.join(_SUPPORTED), name))
         _check_own_baseline("UnsupervisedEmbedding", model, name)
-        want = ReconstructionLoss if name in _S_MODELS else NegativeSamplingLoss
+        want = VAELoss if name == 'VGRNN' else ReconstructionLoss if name in _S_MODELS else NegativeSamplingLoss
         if not isinstance(self.loss, want):
             raise ValueError("%s trains with %s, got %s" % (name, want.__name__, type(self.loss).__name__))
         return name
@@ -175,13 +186,25 @@ class UnsupervisedEmbedding(object):
             del res, emb, struct, loss
         return losses, output_list
 
+    def _epoch_vgrnn(self, model, x_list, adj_list, edge_list, batch_size, fused):
+        """the reference's batch loop for a VGRNN (embedding.py:342-352): every batch a full forward and the full loss"""
+        losses, output_list, hx = [], None, None
+        for _ in batch_bounds(self.node_num, batch_size):
+            output_list, hx, loss_data_list = model(x_list, edge_list, hx, fused=fused)
+            loss = self.loss(loss_data_list + [adj_list])
+            loss.backward()
+            losses.append(float(loss))
+            del loss_data_list, loss
+        return losses, output_list
+
     def learn_embedding(self, adj_list, x_list, edge_list=None, node_dist_list=None, epoch=50, batch_size=1024, lr=1e-3, start_idx=0,
                         weight_decay=0., model_file='ctgcn', load_model=False, shuffle=True, export=True, fused=True):
-        """reference embedding.py:329-368; edge_list is the VGRNN input and unused here; node_dist_list is what a PGNN draws its anchor
-        distances from (required for it, unused otherwise)."""
+        """reference embedding.py:329-368; edge_list is the VGRNN input (required for it, unused otherwise); node_dist_list is what a
+        PGNN draws its anchor distances from (required for it, unused otherwise)."""
         model, loss_model, optimizer = self.prepare(load_model, model_file, lr=lr, weight_decay=weight_decay)
         name = self._check_model(model)
         _check_node_dist(name, node_dist_list)
+        _check_edge_list(name, edge_list, len(x_list))
         all_nodes = torch.arange(self.node_num, device=self.device)
         base = self.sample_seed_base = self._seed_base()
         run = self._epoch_fused if fused else self._epoch_per_batch
@@ -191,7 +214,10 @@ class UnsupervisedEmbedding(object):
         for i in range(epoch):
             node_indices = all_nodes[epoch_order(self.node_num, shuffle).to(self.device)]
             t1 = time.time()
-            self.last_epoch_losses, output_list = run(model, name, x_list, adj_list, node_indices, batch_size, i, base, node_dist_list)
+            if name == 'VGRNN':
+                self.last_epoch_losses, output_list = self._epoch_vgrnn(model, x_list, adj_list, edge_list, batch_size, fused)
+            else:
+                self.last_epoch_losses, output_list = run(model, name, x_list, adj_list, node_indices, batch_size, i, base, node_dist_list)
             optimizer.step()            # gradient accumulation over the epoch's batches (embedding.py:349-352)
             model.zero_grad()
             print('epoch', i + 1, ', batches =', len(self.last_epoch_losses), ', loss:', sum(self.last_epoch_losses),
@@ -360,13 +386,17 @@ class SupervisedEmbedding(object):
         self.split_seed = int(seed)
         return link_splits(edge_list, self.node_num, learning_type, train_ratio, val_ratio, test_ratio, self.split_seed)
 
-    def get_model_res(self, learning_type, adj_list, x_list, edge_list, node_dist_list, batch_indices, model, classifier, hx=None):
+    def get_model_res(self, learning_type, adj_list, x_list, edge_list, node_dist_list, batch_indices, model, classifier, hx=None, fused=True):
         """(loss_input_list, output_list, hx): reference embedding.py:193-226 for the k-core models."""
         if model.method_name in _S_MODELS:
             embedding_list, structure_list = model(x_list, adj_list)
             embedding_list = embedding_list[:-1] if learning_type == 'S-link-dy' else embedding_list
             cls_list = classifier(embedding_list, batch_indices)
             return [cls_list, embedding_list, structure_list], structure_list, hx
+        if model.method_name == 'VGRNN':
+            embedding_list, _, loss_data_list = model(x_list, edge_list, hx, fused=fused)
+            embedding_list = embedding_list[:-1] if learning_type == 'S-link-dy' else embedding_list
+            return loss_data_list + [adj_list, classifier(embedding_list, batch_indices)], embedding_list, hx
         embedding_list = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device)
         embedding_list = embedding_list[:-1] if learning_type == 'S-link-dy' else embedding_list
         return classifier(embedding_list, batch_indices), embedding_list, hx
@@ -376,7 +406,7 @@ class SupervisedEmbedding(object):
         if name not in _SUPPORTED:
             raise NotImplementedError("SupervisedEmbedding covers %s, not %r" % (', '.join(_SUPPORTED), name))
         _check_own_baseline("SupervisedEmbedding", model, name)
-        want = StructureClassificationLoss if name in _S_MODELS else ClassificationLoss
+        want = VAEClassificationLoss if name == 'VGRNN' else StructureClassificationLoss if name in _S_MODELS else ClassificationLoss
         if not isinstance(self.loss, want):
             raise ValueError("%s trains with %s, got %s" % (name, want.__name__, type(self.loss).__name__))
         return name
@@ -388,7 +418,9 @@ class SupervisedEmbedding(object):
         """reference embedding.py:230-290.  train_classifier departs from the reference (see the class).  batch_info: a precomputed
         (idx_train, label_train, idx_val, label_val, idx_test, label_test) used in place of get_batch_info."""
         assert train_ratio + val_ratio + test_ratio <= 1.0
-        _check_node_dist(self._check_model(self.model), node_dist_list)
+        name = self._check_model(self.model)
+        _check_node_dist(name, node_dist_list)
+        _check_edge_list(name, edge_list, len(x_list))
         model, loss_model, optimizer, classifier = self.prepare(load_model, model_file, classifier_file, lr, weight_decay, train_classifier)
         if batch_info is None:
             batch_info = self.get_batch_info(learning_type, node_labels, edge_labels, edge_list, batch_size, shuffle, train_ratio, val_ratio,
@@ -410,7 +442,7 @@ class SupervisedEmbedding(object):
             for i in range(epoch):
                 t1 = time.time()
                 loss_input_list, output_list, _ = self.get_model_res(learning_type, adj_list, x_list, edge_list, node_dist_list, idx_train,
-                                                                     model, classifier)
+                                                                     model, classifier, fused=bool(fused))
                 loss_train, acc_train, auc_train = loss_model(loss_input_list, label_train)
                 loss_train.backward()
                 if self.on_backward is not None:
@@ -424,7 +456,7 @@ class SupervisedEmbedding(object):
                 if i > 0:
                     with torch.no_grad():
                         loss_input_list, output_list, _ = self.get_model_res(learning_type, adj_list, x_list, edge_list, node_dist_list,
-                                                                             idx_val, model, classifier)
+                                                                             idx_val, model, classifier, fused=bool(fused))
                         loss_val, acc_val, auc_val = loss_model(loss_input_list, label_val)
                     rec.update(loss_val=float(loss_val), acc_val=float(acc_val), auc_val=float(auc_val))
                     if rec['acc_val'] > best_acc:
@@ -446,7 +478,7 @@ class SupervisedEmbedding(object):
             classifier.eval()
             with torch.no_grad():
                 loss_input_list, output_list, _ = self.get_model_res(learning_type, adj_list, x_list, edge_list, node_dist_list, idx_test,
-                                                                     model, classifier)
+                                                                     model, classifier, fused=bool(fused))
                 loss_test, acc_test, auc_test = loss_model(loss_input_list, label_test)
             self.test_result = (float(loss_test), float(acc_test), float(auc_test))
             print('Test set results:', 'loss= {:.4f}'.format(self.test_result[0]), 'accuracy= {:.4f}'.format(self.test_result[1]),

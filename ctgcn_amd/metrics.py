@@ -9,6 +9,10 @@ against ONE forward's embeddings, losses and the gradient of their sum by the ke
 
 ClassificationLoss and StructureClassificationLoss are the supervised trainer's losses (reference metrics.py:169-229): cross entropy
 (or BCE with logits for 1-D scores), accuracy and ROC AUC per snapshot, by the loss pass of ctgcn_supervised.hip.
+
+VAELoss and VAEClassificationLoss are the VGRNN baseline's losses (reference metrics.py:126-161, :232-247): the KL divergence of the
+posterior from the prior plus the decoder's weighted BCE against the adjacency, which ops.vae_nll (ctgcn_vgrnn.hip) computes from z
+without the [N, N] matrices when the model hands over its lazy decoder output.
 """
 import ctypes
 import itertools
@@ -339,3 +343,67 @@ class StructureClassificationLoss(nn.Module):
         structure_loss = self.reconstruction_loss([node_embedding, structure_embedding, None])
         cls_loss, total_acc, total_auc = self.classification_loss(cls_res, batch_labels)
         return structure_loss + cls_loss, total_acc, total_auc
+
+
+class VAELoss(nn.Module):
+    """Σ_t KLD(enc_t ‖ prior_t) + NLL(dec_t, adj_t) of the VGRNN (reference metrics.py:126-161).  input_list = [enc_mean, enc_std,
+    prior_mean, prior_std, dec, adj], one entry per snapshot each.  dec[t] is the model's lazy decoder output (an object holding z_t:
+    the loss is ops.vae_nll, no [N, N] matrix) or a dense [N, N] logit matrix (the reference's expression in stock torch ops);
+    adj[t] is a torch sparse tensor or an ops.GcnAdj of the target adjacency, weights included.  The KLD is elementwise torch work,
+    summed in fp64; the result is a fp64 scalar.  An adjacency whose values sum to 0 raises ValueError (the reference divides by zero)."""
+
+    def __init__(self, eps=1e-10):
+        super().__init__()
+        self.eps = eps
+
+    def forward(self, input_list):
+        assert len(input_list) == 6
+        enc_mean_list, enc_std_list, prior_mean_list, prior_std_list, dec_list, adj_list = input_list
+        kld_loss, nll_loss = 0, 0
+        for t in range(len(adj_list)):
+            kld_loss = kld_loss + self._kld_gauss(enc_mean_list[t], enc_std_list[t], prior_mean_list[t], prior_std_list[t])
+            nll_loss = nll_loss + self._nll_bernoulli(dec_list[t], adj_list[t])
+        return kld_loss + nll_loss
+
+    def _kld_gauss(self, mean_1, std_1, mean_2, std_2):
+        num_nodes = mean_1.size()[0]
+        kld_element = (2 * torch.log(std_2 + self.eps) - 2 * torch.log(std_1 + self.eps)
+                       + (torch.pow(std_1 + self.eps, 2) + torch.pow(mean_1 - mean_2, 2)) / torch.pow(std_2 + self.eps, 2) - 1)
+        return (0.5 / num_nodes) * torch.mean(torch.sum(kld_element.double(), dim=1), dim=0)
+
+    @staticmethod
+    def _nll_bernoulli(dec, adj):
+        if not isinstance(dec, torch.Tensor):                  # the lazy decoder output: z, never z zᵀ
+            from .layers import as_gcn_adj
+            return ops.vae_nll(dec.z, as_gcn_adj(adj, dec.z.device, symmetric=False))
+        target = (adj.to_sparse_tensor() if isinstance(adj, ops.GcnAdj) else adj).to_dense().to(dec.dtype)
+        n = target.size()[0]
+        total = target.sum()
+        if float(total) == 0.0:
+            raise ValueError("the adjacency's values sum to 0: pos_weight = (n² − S) / S is undefined")
+        posw = (n * n - total) / total
+        norm = n * n / ((n * n - total) * 2)
+        return norm * torch.mean(F.binary_cross_entropy_with_logits(input=dec, target=target, pos_weight=posw, reduction='none'), dim=[0, 1])
+
+
+class VAEClassificationLoss(nn.Module):
+    """VAELoss(input_list[:-1]) + ClassificationLoss(input_list[-1], labels) for a supervised VGRNN (reference metrics.py:232-247)."""
+
+    def __init__(self, n_class, eps=1e-10):
+        super().__init__()
+        self.vae_loss = VAELoss(eps=eps)
+        self.classification_loss = ClassificationLoss(n_class)
+
+    @property
+    def fused(self):
+        return self.classification_loss.fused
+
+    @fused.setter
+    def fused(self, value):
+        self.classification_loss.fused = bool(value)
+
+    def forward(self, input_list, batch_labels):
+        assert len(input_list) == 7
+        vae_loss = self.vae_loss(input_list[:-1])
+        classification_loss, total_acc, total_auc = self.classification_loss(input_list[-1], batch_labels)
+        return vae_loss + classification_loss, total_acc, total_auc

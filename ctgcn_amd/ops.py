@@ -2922,3 +2922,238 @@ def pgnn_conv(PS, dists_max, dists_argmax, w_p, b_p=None, table=None, need_pos=T
         return (PS.new_zeros(0, prep.A) if need_pos else None), (PS.new_zeros(0, d) if need_struct else None)
     return _PgnnConv.apply(_row_view(PS), table.contiguous(), w_p.contiguous(), None if b_p is None else b_p.reshape(-1).contiguous(), prep,
                            bool(need_pos), bool(need_struct), int(epi), p, key)
+
+
+# ------------------------------------------------------------------------- decoder loss of the VGRNN baseline (ctgcn_vgrnn.hip)
+VAE_NLL_TILE = 32                       # rows and columns of a tile of the dense pass (ctgcn_vae_nll_tile())
+
+
+class _Coefficients(object):
+    """The CSR of a GcnAdj with other values: what _gcn_conv_fwd reads of an adjacency"""
+
+    def __init__(self, adj, val):
+        self.row_ptr, self.col, self.val, self.nnz = adj.row_ptr, adj.col, val, adj.nnz
+        self.long_rows, self.long_threshold, self.workspace = adj.long_rows, adj.long_threshold, adj.workspace
+
+
+def adjacency_sum(adj):
+    """S = the sum of the stored values of a GcnAdj in fp64, once per adjacency (one device-to-host read)"""
+    s = getattr(adj, "_value_sum", None)
+    if s is None:
+        s = adj._value_sum = float(adj.val.double().sum())
+    return s
+
+
+def _vae_nll_raw(z, adj, posw_m1, want_grad):
+    """(Σ_ij softplus(x_ij) + Σ_stored a_e ((posw − 1) softplus(−x_e) − x_e) as a fp64 [1] tensor, its gradient by z or None)"""
+    lib = _lib.load()
+    n, d = z.shape
+    dev = z.device
+    loss = torch.zeros(2, dtype=torch.float64, device=dev)          # an adjacency without stored entries writes no second term
+    dz = torch.empty(n, d, dtype=torch.float32, device=dev) if want_grad else None
+    with torch.cuda.device(dev), _timed("vae_nll", n=n, d=d, nnz=adj.nnz):
+        nbytes = int(lib.ctgcn_vae_nll_workspace_bytes(n, adj.nnz))
+        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        check(lib.ctgcn_vae_nll_dense_f32(n, d, ptr(z), z.stride(0), ptr(dz), d, ptr(loss), ptr(ws), nbytes, _stream()),
+              "ctgcn_vae_nll_dense_f32")
+        for k, a in enumerate((adj, adj.transposed()) if want_grad else (adj,)):
+            coef = torch.empty(a.nnz, dtype=torch.float32, device=dev)
+            check(lib.ctgcn_vae_nll_entries_f32(n, a.nnz, d, ptr(a.row_ptr), ptr(a.col), ptr(a.val), ptr(z), z.stride(0), posw_m1, ptr(coef),
+                                                None if k else loss[1:].data_ptr(), ptr(ws), nbytes, _stream()), "ctgcn_vae_nll_entries_f32")
+            if want_grad and a.nnz:
+                dz += _gcn_conv_fwd(_Coefficients(a, coef), z, None, GCN_EPI_NONE)[0]
+    return loss.sum(0, keepdim=True), dz
+
+
+class _VaeNll(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, adj, n2_minus_s, posw_m1):
+        want_grad = ctx.needs_input_grad[0]
+        total, dz = _vae_nll_raw(z, adj, posw_m1, want_grad)
+        scale = 1.0 / (2.0 * n2_minus_s)
+        if want_grad:
+            ctx.save_for_backward(dz.mul_(scale))
+        return (total * scale).to(torch.float32).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.saved_tensors[0] * g, None, None, None
+
+
+def vae_nll(z, adj):
+    """The reference's VAELoss.__nll_bernoulli(z zᵀ, adj.to_dense()) (metrics.py:154-161) as a fp32 scalar, differentiable in z, with
+    no [n, n] matrix: one tiled pass over z zᵀ on the fp32 matrix cores gives Σ softplus(x_ij) and its gradient, the stored entries of
+    adj (a GcnAdj of the target adjacency as given: its weights count, its pattern need not be symmetric) give the rest.  Sums are kept
+    in fp64 and added in a fixed order.  An adjacency whose values sum to 0 (the reference divides by zero) or to n² raises ValueError."""
+    _need_cuda(z, adj.val)
+    if z.dim() != 2 or z.shape[0] != adj.n:
+        raise ValueError("z must be [%d, d], got %s" % (adj.n, tuple(z.shape)))
+    if z.dtype != torch.float32:
+        raise TypeError("fp32 embeddings expected")
+    if z.device != adj.device:
+        raise ValueError("z on %s but adjacency on %s" % (z.device, adj.device))
+    if z.shape[1] < 1:
+        raise ValueError("z needs at least one column")
+    s = adjacency_sum(adj)
+    n2 = float(adj.n) * float(adj.n)
+    if s == 0.0:
+        raise ValueError("the adjacency's values sum to 0: pos_weight = (n² − S) / S is undefined")
+    if n2 - s == 0.0:
+        raise ValueError("the adjacency's values sum to n²: the loss's norm n² / (2 (n² − S)) is undefined")
+    return _VaeNll.apply(_row_view(z), adj, n2 - s, (n2 - s) / s - 1.0)
+
+
+# ------------------------------------------------------------------------- fused gathers of the VGRNN baseline (ctgcn_vgrnn.hip)
+def _transposed_gather(adj, G):
+    """Âᵀ G: the plain aggregation over the transposed CSR, as gcn_conv's backward does"""
+    return _gcn_conv_fwd(adj.transposed(), G, None, GCN_EPI_NONE)[0]
+
+
+VGRNN_PREP_GATES, VGRNN_PREP_BLEND, VGRNN_PREP_HEADS = 0, 1, 2
+
+
+def _vgrnn_prep(mode, grads, saved, extras, want_db):
+    """(G, extra results, db): ctgcn_vgrnn_bwd_prep_f32, the one N x d pass of a fused gather's backward.  grads: up to three incoming
+    gradients (None counts as zero), saved: the forward's saved [n, w] tensors, extras: how many [n, w] results besides G"""
+    lib = _lib.load()
+    n, w = saved[0].shape
+    segs = (3, 1, 2)[mode]
+    dev = saved[0].device
+    grads = [None if g is None else _row_view(g) for g in grads] + [None] * (3 - len(grads))
+    saved = list(saved) + [None] * (3 - len(saved))
+    G = torch.empty(n, segs * w, dtype=torch.float32, device=dev)
+    out = [torch.empty(n, w, dtype=torch.float32, device=dev) for _ in range(extras)] + [None] * (2 - extras)
+    db = torch.zeros(segs * w, dtype=torch.float32, device=dev) if want_db else None
+    nbytes = int(lib.ctgcn_gcn_conv_prep_workspace_bytes(n, segs * w)) if want_db else 0
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if want_db else None
+    flat = []
+    for t in grads + saved:
+        flat += [ptr(t), 0 if t is None else t.stride(0)]
+    with torch.cuda.device(dev), _timed("vgrnn_bwd_prep", n=n, d=segs * w):
+        check(lib.ctgcn_vgrnn_bwd_prep_f32(mode, n, w, *flat, ptr(G), G.stride(0), ptr(out[0]), ptr(out[1]), ptr(db), ptr(ws), nbytes, _stream()),
+              "ctgcn_vgrnn_bwd_prep_f32")
+    return G, out[:extras], db
+
+
+class _GgruGates(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, U, h, bias, adj):
+        lib = _lib.load()
+        n, H = h.shape
+        z, r, q, c = (torch.empty(n, H, dtype=torch.float32, device=U.device) for _ in range(4))
+        with torch.cuda.device(U.device), _timed("ggru_gates_fwd", n=n, d=3 * H, nnz=adj.nnz):
+            check(lib.ctgcn_ggru_gates_fwd_f32(n, H, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(U), U.stride(0), ptr(bias), ptr(h),
+                                               h.stride(0), ptr(z), ptr(r), ptr(q), ptr(c), *_gcn_long(adj, 3 * H), _stream()),
+                  "ctgcn_ggru_gates_fwd_f32")
+        ctx.adj = adj
+        ctx.save_for_backward(z, r, h)
+        return z, q, c
+
+    @staticmethod
+    def backward(ctx, dz, dq, dc):
+        G, (dh,), db = _vgrnn_prep(VGRNN_PREP_GATES, (dz, dq, dc), ctx.saved_tensors, 1, ctx.needs_input_grad[2])
+        dU = _transposed_gather(ctx.adj, G) if ctx.needs_input_grad[0] else None
+        return dU, dh, db, None
+
+
+class _GgruBlend(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, V, c, z, h, adj):
+        lib = _lib.load()
+        n, H = h.shape
+        h_new, h_tilde = (torch.empty(n, H, dtype=torch.float32, device=V.device) for _ in range(2))
+        with torch.cuda.device(V.device), _timed("ggru_blend_fwd", n=n, d=H, nnz=adj.nnz):
+            check(lib.ctgcn_ggru_blend_fwd_f32(n, H, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(V), V.stride(0), ptr(c), c.stride(0),
+                                               ptr(z), z.stride(0), ptr(h), h.stride(0), ptr(h_new), ptr(h_tilde), *_gcn_long(adj, H),
+                                               _stream()), "ctgcn_ggru_blend_fwd_f32")
+        ctx.adj = adj
+        ctx.save_for_backward(z, h, h_tilde)
+        return h_new
+
+    @staticmethod
+    def backward(ctx, dh_new):
+        G, (dz, dh), _ = _vgrnn_prep(VGRNN_PREP_BLEND, (dh_new,), ctx.saved_tensors, 2, False)     # G: in front of the gather, and dc
+        dV = _transposed_gather(ctx.adj, G) if ctx.needs_input_grad[0] else None
+        return dV, G, dz, dh, None
+
+
+class _VgrnnHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, bias, noise, adj):
+        lib = _lib.load()
+        n, out = noise.shape
+        mean, std, z = (torch.empty(n, out, dtype=torch.float32, device=S.device) for _ in range(3))
+        with torch.cuda.device(S.device), _timed("vgrnn_heads_fwd", n=n, d=2 * out, nnz=adj.nnz):
+            check(lib.ctgcn_vgrnn_heads_fwd_f32(n, out, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(S), S.stride(0), ptr(bias), ptr(noise),
+                                                noise.stride(0), ptr(mean), ptr(std), ptr(z), *_gcn_long(adj, 2 * out), _stream()),
+                  "ctgcn_vgrnn_heads_fwd_f32")
+        ctx.adj = adj
+        ctx.save_for_backward(std, noise)
+        return mean, std, z
+
+    @staticmethod
+    def backward(ctx, dmean, dstd, dz):
+        # softplus' = σ(pre) = 1 − exp(−std); above the threshold std = pre and the factor rounds to 1
+        G, _, db = _vgrnn_prep(VGRNN_PREP_HEADS, (dmean, dstd, dz), ctx.saved_tensors, 0, ctx.needs_input_grad[1])
+        return (_transposed_gather(ctx.adj, G) if ctx.needs_input_grad[0] else None), db, None, None
+
+
+def _check_rows(adj, width, **tensors):
+    """fp32 [adj.n, width] CUDA operands on the adjacency's device, as row views; None passes"""
+    out = []
+    for name, (t, w) in tensors.items():
+        if t is None:
+            out.append(None)
+            continue
+        if t.dim() != 2 or tuple(t.shape) != (adj.n, w):
+            raise ValueError("%s must be [%d, %d], got %s" % (name, adj.n, w, tuple(t.shape)))
+        if t.dtype != torch.float32:
+            raise TypeError("fp32 %s expected" % name)
+        if t.device != adj.device:
+            raise ValueError("%s on %s but adjacency on %s" % (name, t.device, adj.device))
+        out.append(_row_view(t))
+    return out
+
+
+def _check_bias(bias, width, device):
+    if bias is None:
+        return None
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (width,) or bias.device != device:
+        raise ValueError("bias must be fp32 [%d] on %s" % (width, device))
+    return bias.contiguous()
+
+
+def ggru_gates(U, h, adj, bias=None):
+    """(z, q, c) of a graph-GRU step's first pass (reference baseline/vgrnn.py:384-386) from one gather of width 3 H:
+    [g_z | g_r | g_c] = Â U + bias, z = σ(g_z), q = σ(g_r) ∘ h, c = g_c, with U = x [W_xz | W_xr | W_xh] + h [W_hz | W_hr | 0] and the
+    summed biases.  Differentiable in U, h and bias: one N x 3H pre-pass on the saved z, r and h (the gradient in front of the gather, dh,
+    the bias gradient by per-block column sums), then the plain aggregation over adj.transposed()."""
+    _need_cuda(U, h, adj.val, bias)
+    if h.dim() != 2:
+        raise ValueError("h must be [n, H]")
+    H = h.shape[1]
+    U, h = _check_rows(adj, H, U=(U, 3 * H), h=(h, H))
+    return _GgruGates.apply(U, h, _check_bias(bias, 3 * H, adj.device), adj)
+
+
+def ggru_blend(V, c, z, h, adj):
+    """h' = z ∘ h + (1 − z) ∘ tanh(c + Â V) (reference baseline/vgrnn.py:386-387) from one gather of width H, V = q W_hh.
+    Differentiable in V, c, z and h."""
+    _need_cuda(V, c, z, h, adj.val)
+    if h.dim() != 2:
+        raise ValueError("h must be [n, H]")
+    H = h.shape[1]
+    V, c, z, h = _check_rows(adj, H, V=(V, H), c=(c, H), z=(z, H), h=(h, H))
+    return _GgruBlend.apply(V, c, z, h, adj)
+
+
+def vgrnn_heads(S, adj, bias, noise):
+    """(mean, std, z) of the VGRNN encoder's twin heads (reference baseline/vgrnn.py:498-507) from one gather of width 2 out:
+    [g_m | g_s] = Â S + bias, mean = g_m, std = F.softplus(g_s), z = mean + noise ∘ std, with S = enc [W_mean | W_std].
+    Differentiable in S and bias; noise is an operand (torch.randn from torch's generator, so torch.manual_seed reproduces a run)."""
+    _need_cuda(S, adj.val, bias, noise)
+    if noise.dim() != 2:
+        raise ValueError("noise must be [n, out]")
+    out = noise.shape[1]
+    S, noise = _check_rows(adj, out, S=(S, 2 * out), noise=(noise.detach(), out))
+    return _VgrnnHeads.apply(S, _check_bias(bias, 2 * out, adj.device), noise, adj)

@@ -1080,6 +1080,64 @@ size_t ctgcn_pgnn_table_grad_workspace_bytes(int64_t n_pieces);
 int ctgcn_pgnn_table_grad_f32(int64_t items, int32_t n_table, const float *gd, const int32_t *perm, const int32_t *pieces, int64_t n_pieces,
                               const int32_t *piece_ptr, float *g_table, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- decoder loss of the VGRNN baseline (ctgcn_vgrnn.hip): reference baseline/vgrnn.py:402-413 and metrics.py:154-161 without a dense
+ * [n, n] matrix.  With S the sum of the stored adjacency values, posw = (n² − S) / S and x_ij = z_i · z_j,
+ *   nll = [ Σ_ij softplus(x_ij) + Σ_stored a_e ((posw − 1) softplus(−x_e) − x_e) ] / (2 (n² − S)).
+ * ctgcn_vae_nll_dense_f32: loss[0] (fp64, device) = Σ_ij softplus(x_ij) and, when dZ is not null, dZ[i] = 2 Σ_j sigmoid(x_ij) z_j, from
+ *   one tiled pass over Z Zᵀ on the exact-fp32 matrix cores; a wave owns ctgcn_vae_nll_tile() rows and walks every column tile, rows
+ *   and columns beyond n masked out of both sums.  Z [n, d] fp32 with row stride ldz; any d >= 1 (above 128 one launch per 128
+ *   columns of dZ).
+ * ctgcn_vae_nll_entries_f32: per stored entry e = (i, j) of the CSR, coef[e] = a_e (−posw_m1 sigmoid(−x_e) − 1), the derivative of the
+ *   entry's term by x_e, and, when loss is not null, loss[0] = Σ_e a_e (posw_m1 softplus(−x_e) − x_e) in fp64.  dZ += C Z + Cᵀ Z with
+ *   C the CSR holding coef is then the plain aggregation (ctgcn_gcn_conv_fwd_f32) over the CSR and its transpose.
+ * workspace: ctgcn_vae_nll_workspace_bytes(n, nnz) bytes, 8-byte aligned (the entries call needs it only with loss).  Returns
+ * CTGCN_E_INVALID for null pointers and bad sizes, CTGCN_E_WORKSPACE for a workspace that is too small; n = 0 or nnz = 0 writes
+ * nothing.  No atomics: partial sums are fp64 and added in a fixed order, repeated calls are bit-identical.
+ */
+int32_t ctgcn_vae_nll_tile(void);
+size_t ctgcn_vae_nll_workspace_bytes(int64_t n, int64_t nnz);
+int ctgcn_vae_nll_dense_f32(int64_t n, int32_t d, const float *Z, int64_t ldz, float *dZ, int64_t lddz, double *loss, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int ctgcn_vae_nll_entries_f32(int64_t n, int64_t nnz, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val,
+                              const float *Z, int64_t ldz, double posw_m1, float *coef, double *loss, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* ---- fused gathers of the VGRNN baseline (ctgcn_vgrnn.hip; reference baseline/vgrnn.py:380-397, :497-508) over a normalised CSR, on
+ * the row-gather scaffold of ctgcn_gcn_conv_fwd_f32 (same long-row arguments and workspace rule, sized for the gathered width).  Every
+ * result is [n, width] fp32 with row stride width; inputs have unit column stride and the given row strides.
+ * ctgcn_ggru_gates_fwd_f32: [g_z | g_r | g_c] = Â U + bias with U [n, 3 hid] and bias [3 hid] or null;
+ *   z = σ(g_z), r = σ(g_r), q = r ∘ h, c = g_c.
+ * ctgcn_ggru_blend_fwd_f32: h_tilde = tanh(c + Â V) with V [n, hid]; h_new = z ∘ h + (1 − z) ∘ h_tilde.
+ * ctgcn_vgrnn_heads_fwd_f32: [g_m | g_s] = Â S + bias with S [n, 2 out] and bias [2 out] or null; mean = g_m,
+ *   std = softplus(g_s) (g_s above 20 is passed through, as F.softplus does), z = mean + noise ∘ std.
+ * ctgcn_vgrnn_bwd_prep_f32: the one N x d pass of each backward.  G [n, segments x width] = the gradient in front of the gather, which the
+ *   plain aggregation over the transposed CSR (ctgcn_gcn_conv_fwd_f32) then takes to the source; db [segments x width], when not null,
+ *   = the column sums of G, per-block partial sums added in block order (workspace: ctgcn_gcn_conv_prep_workspace_bytes(n, segments x
+ *   width) bytes, 16-byte aligned).  An incoming gradient that is null counts as zero.  x0, x1 are [n, width] with row stride width.
+ *     mode 0 (gates, 3 segments): g = dz, dq, dc; s = z, r, h: G = [dz z (1 − z) | dq h r (1 − r) | dc], x0 = dh = dq r
+ *     mode 1 (blend, 1 segment):  g0 = dh' (required); s = z, h, h_tilde: G = dh' (1 − z) (1 − h_tilde²), x0 = dz = dh' (h − h_tilde),
+ *                                 x1 = dh = dh' z; no db
+ *     mode 2 (heads, 2 segments): g = dmean, dstd, dz; s = std, noise: G = [dmean + dz | (dstd + dz noise) (1 − exp(−std))]
+ * Returns CTGCN_E_INVALID for null pointers and bad sizes, CTGCN_E_UNSUPPORTED for more than 65535 long rows, CTGCN_E_WORKSPACE for a
+ * workspace that is too small; 0 for n = 0.  No atomics; repeated calls are bit-identical.
+ */
+int ctgcn_vgrnn_bwd_prep_f32(int32_t mode, int64_t n, int32_t width, const float *g0, int64_t ldg0, const float *g1, int64_t ldg1,
+                             const float *g2, int64_t ldg2, const float *s0, int64_t lds0, const float *s1, int64_t lds1, const float *s2,
+                             int64_t lds2, float *G, int64_t ldG, float *x0, float *x1, float *db, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int ctgcn_ggru_gates_fwd_f32(int64_t n, int32_t hid, const int32_t *row_ptr, const int32_t *col, const float *val, const float *U, int64_t ldu,
+                             const float *bias, const float *h, int64_t ldh, float *z, float *r, float *q, float *c,
+                             const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int ctgcn_ggru_blend_fwd_f32(int64_t n, int32_t hid, const int32_t *row_ptr, const int32_t *col, const float *val, const float *V, int64_t ldv,
+                             const float *c, int64_t ldc, const float *z, int64_t ldz, const float *h, int64_t ldh, float *h_new,
+                             float *h_tilde, const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace,
+                             size_t workspace_bytes, void *stream);
+int ctgcn_vgrnn_heads_fwd_f32(int64_t n, int32_t out, const int32_t *row_ptr, const int32_t *col, const float *val, const float *S, int64_t lds,
+                              const float *bias, const float *noise, int64_t ldnoise, float *mean, float *std_out, float *z,
+                              const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
+                              void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
