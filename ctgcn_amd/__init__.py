@@ -14,11 +14,15 @@ from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLo
                       VAELoss)
 from .embedding import SupervisedEmbedding, UnsupervisedEmbedding  # noqa: F401
 from .baseline import (GAT, GCN, GCRN, GIN, PGNN, SAGE, Aggregator, EvolveGCN, GraphConvolution, Nonlinear, PGNN_layer,  # noqa: F401
-                       SAGE_Layer, SpGraphAttentionLayer, VGRNN, GCNConv, InnerProductDecoder, graph_gru_gcn)
+                       SAGE_Layer, SpGraphAttentionLayer, VGRNN, GCNConv, InnerProductDecoder, graph_gru_gcn, BatchGenerator, BatchPredictor,
+                       DynAE, DynamicEmbedding, DynGraph2VecLoss, RegularizationLoss, DynGEM, DynGEMBatchGenerator, DynGEMBatchPredictor,
+                       DynGEMLoss)
 from .evaluation import DataGenerator, LinkPredictor, aggregate_results, evaluate, evaluate_window, link_prediction  # noqa: F401
 
 __all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoader", "NegativeSamplingLoss", "ReconstructionLoss",
            "UnsupervisedEmbedding", "SupervisedEmbedding", "MLPClassifier", "InnerProduct", "EdgeClassifier", "ClassificationLoss",
            "StructureClassificationLoss", "DataGenerator", "LinkPredictor", "aggregate_results", "evaluate", "evaluate_window", "link_prediction", "EvolveGCN",
            "GCN", "GraphConvolution", "GCRN", "GAT", "SpGraphAttentionLayer", "GIN", "SAGE", "SAGE_Layer", "Aggregator", "PGNN", "PGNN_layer", "Nonlinear",
-           "VGRNN", "GCNConv", "graph_gru_gcn", "InnerProductDecoder", "VAELoss", "VAEClassificationLoss"]
+           "VGRNN", "GCNConv", "graph_gru_gcn", "InnerProductDecoder", "VAELoss", "VAEClassificationLoss",
+           "DynAE", "RegularizationLoss", "DynGraph2VecLoss", "BatchGenerator", "BatchPredictor", "DynamicEmbedding", "DynGEM", "DynGEMLoss",
+           "DynGEMBatchGenerator", "DynGEMBatchPredictor"]

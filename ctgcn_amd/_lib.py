@@ -207,6 +207,12 @@ SIGNATURES = {
     "ctgcn_ggru_blend_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _sz,
                                         _vp]),
     "ctgcn_vgrnn_heads_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_rowsel_max_slots": (_i32, []),
+    "ctgcn_rowsel_conv_fwd_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_rowsel_bucket_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "ctgcn_wrecon_loss_workspace_bytes": (_sz, [_i64, _i64]),
+    "ctgcn_wrecon_loss_f32": (_int, [_i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _c.c_double, _vp, _c.c_double, _i32, _vp, _i64, _vp, _vp,
+                                     _sz, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

@@ -3157,3 +3157,282 @@ def vgrnn_heads(S, adj, bias, noise):
     out = noise.shape[1]
     S, noise = _check_rows(adj, out, S=(S, 2 * out), noise=(noise.detach(), out))
     return _VgrnnHeads.apply(S, _check_bias(bias, 2 * out, adj.device), noise, adj)
+
+
+# ------------------------------------------------------------------------- row-selected passes of the DynGEM / DynAE baselines (ctgcn_dyngem.hip)
+class SnapshotRows(object):
+    """The T snapshots of a window as one stacked CSR on the device: row t N + v is row v of snapshot t, columns are node ids, int32
+    indices and fp32 values, canonical (columns sorted, duplicates summed).  A stored zero stays stored and counts as absent wherever the
+    reference tests x != 0.  Also: row_sum, the weight sum of every row in fp64 rounded once (DynGEM's divisor); transposed(), the
+    stack's transpose as a GcnAdj of N rows with columns in [0, T N), built once by a stable sort; and a host copy of the CSR, whose
+    row lengths size every batch's long-position list and staging area without a device read-back.  Built from scipy matrices, as
+    DataLoader.get_date_adj_list(..., data_type='matrix') returns them."""
+    LONG_POSITION = 2048
+
+    def __init__(self, mats, device, long_threshold=None):
+        import numpy as np
+        import scipy.sparse as sp
+        mats = [sp.csr_matrix(m) for m in (mats if isinstance(mats, (list, tuple)) else [mats])]
+        if not mats:
+            raise ValueError("at least one snapshot expected")
+        n = mats[0].shape[0]
+        for m in mats:
+            if m.shape != (n, n):
+                raise ValueError("every snapshot must be [%d, %d], got %s" % (n, n, m.shape))
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise _lib.CtgcnHipError("ctgcn_amd runs on MI355X only: SnapshotRows on %s. There is no CPU fallback." % device)
+        csr = sp.vstack(mats, format='csr')
+        csr.sum_duplicates()
+        csr.sort_indices()
+        if csr.nnz >= 2 ** 31 or csr.shape[0] >= 2 ** 31:
+            raise ValueError("more than 2^31-1 rows or stored entries")
+        self.T, self.n, self.rows, self.nnz = len(mats), n, len(mats) * n, int(csr.nnz)
+        self.device = device
+        self.long_threshold = int(self.LONG_POSITION if long_threshold is None else long_threshold)
+        if self.long_threshold < 1:
+            raise ValueError("long_threshold must be >= 1")
+        self.host_ptr = csr.indptr.astype(np.int64)
+        self.host_col = csr.indices.astype(np.int32)
+        self.host_val = csr.data.astype(np.float32)
+        self.host_len = np.diff(self.host_ptr)
+        row_of = np.repeat(np.arange(self.rows), self.host_len)
+        sums = np.bincount(row_of, weights=self.host_val.astype(np.float64), minlength=self.rows)
+        self.row_ptr = torch.from_numpy(self.host_ptr.astype(np.int32)).to(device)
+        self.col = torch.from_numpy(self.host_col).to(device)
+        self.val = torch.from_numpy(self.host_val).to(device)
+        self.row_sum = torch.from_numpy(sums.astype(np.float32)).to(device)
+        self._transposed = None
+        self._ws = {}
+
+    @classmethod
+    def from_scipy(cls, mats, device, long_threshold=None):
+        return cls(mats, device, long_threshold)
+
+    def transposed(self):
+        """the stack's transpose: a GcnAdj of N rows whose columns are stacked row ids, rows ascending within a column"""
+        if self._transposed is None:
+            counts = (self.row_ptr[1:] - self.row_ptr[:-1]).to(torch.int64)
+            row = torch.repeat_interleave(torch.arange(self.rows, device=self.device), counts)
+            col = self.col.to(torch.int64)
+            order = torch.argsort(col, stable=True)
+            row_ptr = torch.zeros(self.n + 1, dtype=torch.int64, device=self.device)
+            row_ptr[1:] = torch.bincount(col, minlength=self.n).cumsum(0)
+            self._transposed = GcnAdj(row_ptr.to(torch.int32), row[order].to(torch.int32), self.val[order], self.long_threshold)
+        return self._transposed
+
+    def select(self, idx):
+        return idx if isinstance(idx, RowSelection) else RowSelection(self, idx)
+
+    def snapshot(self, t):
+        """snapshot t as a scipy CSR (host copy)"""
+        import scipy.sparse as sp
+        lo, hi = self.host_ptr[t * self.n], self.host_ptr[(t + 1) * self.n]
+        return sp.csr_matrix((self.host_val[lo:hi], self.host_col[lo:hi], self.host_ptr[t * self.n:(t + 1) * self.n + 1] - lo), shape=(self.n, self.n))
+
+    def dense(self, idx):
+        """the selected rows as a dense [B, L, N] fp32 tensor (-1: a zero row), made on the device with stock torch ops: the composed
+        path's input"""
+        sel = self.select(idx)
+        ix = sel.idx.to(torch.int64)
+        B, L = ix.shape
+        safe = ix.clamp(min=0).reshape(-1)
+        start = self.row_ptr.to(torch.int64)[safe]
+        cnt = torch.where(ix.reshape(-1) >= 0, self.row_ptr.to(torch.int64)[safe + 1] - start, torch.zeros_like(start))
+        slot = torch.repeat_interleave(torch.arange(B * L, device=self.device), cnt)
+        first = torch.cumsum(cnt, 0) - cnt
+        e = start[slot] + (torch.arange(slot.numel(), device=self.device) - first[slot])
+        out = torch.zeros(B * L, self.n, dtype=torch.float32, device=self.device)
+        out[slot, self.col.to(torch.int64)[e]] = self.val[e]
+        return out.view(B, L, self.n)
+
+    def workspace(self, key, nbytes):
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._ws[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+        return ws
+
+
+class RowSelection(object):
+    """A batch of stacked row ids of a SnapshotRows: idx [B] or [B, L] as host integers (-1: an empty row), uploaded once as int32.
+    From the host copy of the row lengths: the positions with more than long_threshold entries and the pieces their longest is cut into
+    (the contract of ctgcn_gather.h), and ent_ptr, the running sums of the lengths.  inverted(s): per stacked row the batch positions
+    whose slot s selected it, ascending, from a stable sort on the device."""
+
+    def __init__(self, rows, idx):
+        import numpy as np
+        if isinstance(idx, torch.Tensor):
+            idx = idx.detach().cpu().numpy()
+        idx = np.asarray(idx)
+        if idx.dtype.kind not in 'iu':
+            raise TypeError("integer row ids expected")
+        idx = idx.astype(np.int64)
+        if idx.ndim == 1:
+            idx = idx[:, None]
+        if idx.ndim != 2 or idx.shape[1] < 1:
+            raise ValueError("idx must be [B] or [B, L]")
+        if idx.size and (idx.min() < -1 or idx.max() >= rows.rows):
+            raise ValueError("row id outside [-1, %d)" % rows.rows)
+        self.rows, self.host_idx = rows, idx
+        self.B, self.L = idx.shape
+        lens = np.where(idx >= 0, rows.host_len[np.maximum(idx, 0)], 0)
+        self.host_len = lens.sum(1)
+        self.idx = torch.from_numpy(idx.astype(np.int32)).to(rows.device)
+        self.long_pos, self.pieces = None, 1
+        top = int(self.host_len.max()) if self.B else 0
+        if top > rows.long_threshold:
+            self.long_pos = torch.from_numpy(np.nonzero(self.host_len > rows.long_threshold)[0].astype(np.int32)).to(rows.device)
+            piece = GCN_PIECE_FACTOR * rows.long_threshold
+            self.pieces = (top + piece - 1) // piece
+        self._inv, self._ent = {}, None
+
+    def inverted(self, s):
+        hit = self._inv.get(s)
+        if hit is None:
+            col = self.idx[:, s].to(torch.int64)
+            vals, order = torch.sort(torch.where(col >= 0, col, torch.full_like(col, self.rows.rows)), stable=True)
+            inv_ptr = torch.searchsorted(vals, torch.arange(self.rows.rows + 1, device=col.device))
+            hit = self._inv[s] = (inv_ptr.to(torch.int32), order.to(torch.int32))
+        return hit
+
+    def ent_ptr(self):
+        """(int64 [B + 1] on the device, total) of a selection with one row per position"""
+        import numpy as np
+        if self._ent is None:
+            run = np.zeros(self.B + 1, dtype=np.int64)
+            np.cumsum(self.host_len, out=run[1:])
+            self._ent = (torch.from_numpy(run).to(self.rows.device), int(run[-1]))
+        return self._ent
+
+
+def _rowsel_fwd(S, rows, sel, bias, relu, col_stride):
+    lib = _lib.load()
+    d = S.shape[1]
+    Y = torch.empty(sel.B, d, dtype=torch.float32, device=S.device)
+    n_long = 0 if sel.long_pos is None else sel.long_pos.numel()
+    nbytes = n_long * sel.pieces * ((d + 3) // 4 * 4) * 4
+    ws = rows.workspace(("rowsel", d), nbytes) if n_long else None
+    with torch.cuda.device(S.device), _timed("rowsel_conv_fwd", n=sel.B, d=d, nnz=int(sel.host_len.sum())):
+        check(lib.ctgcn_rowsel_conv_fwd_f32(sel.B, sel.L, d, ptr(sel.idx), ptr(rows.row_ptr), ptr(rows.col), ptr(rows.val), ptr(S), S.stride(0),
+                                            col_stride, ptr(bias), 1 if relu else 0, ptr(Y), Y.stride(0), ptr(sel.long_pos), n_long,
+                                            rows.long_threshold, ptr(ws), nbytes, _stream()), "ctgcn_rowsel_conv_fwd_f32")
+    return Y
+
+
+def _rowsel_bucket(sel, s, G):
+    lib = _lib.load()
+    d = G.shape[1]
+    inv_ptr, inv_pos = sel.inverted(s)
+    out = torch.empty(sel.rows.rows, d, dtype=torch.float32, device=G.device)
+    with torch.cuda.device(G.device), _timed("rowsel_bucket", n=sel.rows.rows, d=d):
+        check(lib.ctgcn_rowsel_bucket_f32(sel.rows.rows, d, ptr(inv_ptr), ptr(inv_pos), ptr(G), G.stride(0), ptr(out), out.stride(0), _stream()),
+              "ctgcn_rowsel_bucket_f32")
+    return out
+
+
+def _stack_gather_t(rows, src, out):
+    """out [N, d] = Mᵀ src for the stacked matrix M [T N, N] and src [T N, d]: the plain aggregation over rows.transposed()"""
+    lib = _lib.load()
+    adj = rows.transposed()
+    d = src.shape[1]
+    with torch.cuda.device(src.device), _timed("gcn_conv_fwd", n=adj.n, d=d, nnz=adj.nnz):
+        check(lib.ctgcn_gcn_conv_fwd_f32(adj.n, d, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(src), src.stride(0), None, ptr(out),
+                                         out.stride(0), GCN_EPI_NONE, 0.0, 0, None, *_gcn_long(adj, d), _stream()), "ctgcn_gcn_conv_fwd_f32")
+    return out
+
+
+class _RowselConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, bias, rows, sel, relu, col_stride):
+        Y = _rowsel_fwd(S, rows, sel, bias, relu, col_stride)
+        ctx.rows, ctx.sel, ctx.relu, ctx.col_stride, ctx.s_shape = rows, sel, relu, col_stride, tuple(S.shape)
+        ctx.save_for_backward(*((Y,) if relu else ()))
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        Y = ctx.saved_tensors[0] if ctx.relu else None
+        rows, sel = ctx.rows, ctx.sel
+        G, db = _gcn_conv_prep(_row_view(dY), Y, None, GCN_EPI_RELU if ctx.relu else GCN_EPI_NONE, want_db=ctx.needs_input_grad[1])
+        dS = None
+        if ctx.needs_input_grad[0]:
+            dS = torch.zeros(ctx.s_shape, dtype=torch.float32, device=dY.device)
+            apart = sel.L == 1 or ctx.col_stride >= rows.n                  # the slots' blocks of S do not overlap
+            for s in range(sel.L):
+                block = dS[s * ctx.col_stride:s * ctx.col_stride + rows.n]
+                bucket = _rowsel_bucket(sel, s, G)
+                if apart:
+                    _stack_gather_t(rows, bucket, block)
+                else:
+                    block += _stack_gather_t(rows, bucket, torch.empty_like(block))
+        return dS, db, None, None, None, None
+
+
+def rowsel_conv(S, rows, idx, bias=None, relu=False, col_stride=0):
+    """Y[b] = epi(bias + Σ_s Σ_{e ∈ row idx[b, s]} val[e] S[s col_stride + col[e]]): the first Linear of an MLP over the adjacency rows
+    idx selects from a SnapshotRows (host integers [B] or [B, L], -1 an empty row, or a prepared RowSelection), without the dense
+    [B, L N] input.  S is the transposed weight, [L N, d] with col_stride = N for DynAE, [N, d] for DynGEM.  Differentiable in S and
+    bias: the pre-pass of gcn_conv, bucket sums of its result per stacked row from an inverted index, and the plain aggregation over
+    the transposed stack; no atomics, repeated calls are bit-identical."""
+    _need_cuda(S, bias, rows.val)
+    sel = rows.select(idx)
+    if sel.rows is not rows:
+        raise ValueError("the selection belongs to another SnapshotRows")
+    if S.dim() != 2 or S.shape[1] < 1:
+        raise ValueError("S must be [rows, d]")
+    if S.dtype != torch.float32:
+        raise TypeError("fp32 S expected")
+    if S.device != rows.device:
+        raise ValueError("S on %s but the snapshots on %s" % (S.device, rows.device))
+    col_stride = int(col_stride)
+    if col_stride < 0 or S.shape[0] < (sel.L - 1) * col_stride + rows.n:
+        raise ValueError("S needs at least (L - 1) col_stride + N = %d rows, got %d" % ((sel.L - 1) * max(col_stride, 0) + rows.n, S.shape[0]))
+    if sel.L > int(_lib.load().ctgcn_rowsel_max_slots()):
+        raise ValueError("at most %d rows per batch position" % int(_lib.load().ctgcn_rowsel_max_slots()))
+    return _RowselConv.apply(_row_view(S), _check_bias(bias, S.shape[1], S.device), rows, sel, bool(relu), col_stride)
+
+
+class _WreconLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Z, rows, sel, beta, divide, scale, relu, overwrite):
+        lib = _lib.load()
+        B, N = Z.shape
+        dev = Z.device
+        want_grad = ctx.needs_input_grad[0]
+        dZ = (Z.detach() if overwrite else torch.empty(B, N, dtype=torch.float32, device=dev)) if want_grad else None
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ent_ptr, entries = sel.ent_ptr()
+        nbytes = int(lib.ctgcn_wrecon_loss_workspace_bytes(B, entries))
+        ws = rows.workspace("wrecon", nbytes)
+        with torch.cuda.device(dev), _timed("wrecon_loss", n=B, d=N, nnz=entries):
+            check(lib.ctgcn_wrecon_loss_f32(B, N, ptr(Z), Z.stride(0), ptr(sel.idx), ptr(ent_ptr), entries, ptr(rows.row_ptr), ptr(rows.col),
+                                            ptr(rows.val), beta, ptr(rows.row_sum) if divide else None, scale, 1 if relu else 0, ptr(dZ),
+                                            0 if dZ is None else dZ.stride(0), ptr(loss), ptr(ws), nbytes, _stream()), "ctgcn_wrecon_loss_f32")
+        ctx.dz, ctx.overwrite = dZ, overwrite
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        # an overwriting call owns Z's memory: no second [B, N] tensor (such a graph is walked once)
+        return (ctx.dz.mul_(g) if ctx.overwrite else ctx.dz * g), None, None, None, None, None, None, None
+
+
+def wrecon_loss(Z, rows, tgt, beta, divide=False, scale=1.0, relu=True, overwrite=False):
+    """scale Σ_b Σ_j ((p_bj − x_bj) pen_bj)² / div_b as a fp32 scalar, differentiable in Z: the reconstruction term of DynGEMLoss and
+    DynGraph2VecLoss.  p = relu(Z) (relu=True: Z is the last decoder layer's pre-activation) or Z; x_b is row tgt[b] of the
+    SnapshotRows (host integers [B] or a RowSelection, -1 an all-zero row); pen is beta where x != 0 and 1 elsewhere; div_b the row's
+    weight sum with divide, else 1.  One sweep of Z and a correction at the stored entries: no dense target or penalty tensor.
+    overwrite=True lets the gradient take Z's own memory: Z must not be read afterwards, and the backward may run once."""
+    _need_cuda(Z, rows.val)
+    sel = rows.select(tgt)
+    if sel.rows is not rows:
+        raise ValueError("the selection belongs to another SnapshotRows")
+    if sel.L != 1:
+        raise ValueError("one target row per batch position expected")
+    if Z.dim() != 2 or tuple(Z.shape) != (sel.B, rows.n):
+        raise ValueError("Z must be [%d, %d], got %s" % (sel.B, rows.n, tuple(Z.shape)))
+    if Z.dtype != torch.float32:
+        raise TypeError("fp32 Z expected")
+    if Z.device != rows.device:
+        raise ValueError("Z on %s but the snapshots on %s" % (Z.device, rows.device))
+    return _WreconLoss.apply(_row_view(Z), rows, sel, float(beta), bool(divide), float(scale), bool(relu), bool(overwrite))

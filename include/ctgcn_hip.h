@@ -1138,6 +1138,41 @@ int ctgcn_vgrnn_heads_fwd_f32(int64_t n, int32_t out, const int32_t *row_ptr, co
                               const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
                               void *stream);
 
+/* ---- row-selected passes of the DynGEM and DynAE baselines (ctgcn_dyngem.hip; reference baseline/dynGEM.py, baseline/dynAE.py) over a
+ * window of snapshots stacked into one CSR: row t N + v is row v of snapshot t, columns are node ids, int32 indices, fp32 values.
+ * ctgcn_rowsel_conv_fwd_f32: Y[b] = epi(bias + Σ_{s < slots} Σ_{e ∈ row idx[b][s]} val[e] S[s col_stride + col[e]]) for b < n: the first
+ *   Linear of an MLP over dense adjacency rows, as a gather.  idx [n][slots] holds stacked row ids, -1 an empty row; epi 0 none,
+ *   1 ReLU; Y [n, d] with row stride ldy, S with row stride lds, bias [d] or null; 1 <= slots <= ctgcn_rowsel_max_slots().  On the
+ *   row-gather scaffold of ctgcn_gcn_conv_fwd_f32 with batch positions in the role of rows: a position's entries are those of its
+ *   rows, slot after slot; long_pos lists the positions with more than long_threshold entries, cut into pieces by the same rule and
+ *   with the same workspace rule.  The caller keeps every idx below the CSR's row count and s col_stride + col inside S.
+ * ctgcn_rowsel_bucket_f32: out[r] = Σ G[inv_pos[k]] over inv_ptr[r] <= k < inv_ptr[r + 1], in that order, for r < rows; a row
+ *   without positions is written as zeros.  With inv the inverted index of one slot of idx (per stacked row its batch positions,
+ *   ascending), dS of that slot is the plain aggregation (ctgcn_gcn_conv_fwd_f32) of out over the transposed stack.
+ * ctgcn_wrecon_loss_f32: with p = relu ? max(z, 0) : z and the stored entries (j, v), v != 0, of row tgt[b] (-1: none),
+ *     l_b = (Σ_j p_bj² + Σ_stored (β² (p_bj − v)² − p_bj²)) / div_b,   loss[0] = scale Σ_b l_b   (fp32, device)
+ *   which is Σ_j ((p_bj − x_bj) pen_bj)² / div_b for the dense target row x and pen = β where x != 0, 1 elsewhere.  div is indexed
+ *   by stacked row id (div_b = div[tgt[b]], 0 for tgt -1) or null for 1.  dZ, when not null, receives d loss / d Z (zero where the
+ *   ReLU was inactive) and may be Z itself.  ent_ptr [n + 1] (int64) are the running sums of the targets' row lengths and entries =
+ *   ent_ptr[n]: z at the stored columns is staged there before the sweep of the row may overwrite it; a row whose ent_ptr does not
+ *   match its length gets a NaN loss.  A row's sweep and its correction run in one workgroup, in that order; row sums are fp64 and
+ *   added in row order; the float4 and the scalar form (width, strides, bases) add the same numbers in the same order, so the loss
+ *   with and without dZ is the same bit pattern.  workspace: ctgcn_wrecon_loss_workspace_bytes(n, entries) bytes, 16-byte aligned.
+ * Returns CTGCN_E_INVALID for null pointers and bad sizes, CTGCN_E_UNSUPPORTED for more than 65535 long positions, CTGCN_E_WORKSPACE for
+ * a workspace that is too small; n = 0 writes nothing (the loss call: loss[0] = 0).  No atomics; repeated calls are bit-identical.
+ */
+int32_t ctgcn_rowsel_max_slots(void);
+int ctgcn_rowsel_conv_fwd_f32(int64_t n, int32_t slots, int32_t d, const int32_t *idx, const int32_t *row_ptr, const int32_t *col,
+                              const float *val, const float *S, int64_t lds, int64_t col_stride, const float *bias, int32_t epi, float *Y,
+                              int64_t ldy, const int32_t *long_pos, int32_t n_long, int32_t long_threshold, void *workspace,
+                              size_t workspace_bytes, void *stream);
+int ctgcn_rowsel_bucket_f32(int64_t rows, int32_t d, const int32_t *inv_ptr, const int32_t *inv_pos, const float *G, int64_t ldg, float *out,
+                            int64_t ldout, void *stream);
+size_t ctgcn_wrecon_loss_workspace_bytes(int64_t n, int64_t entries);
+int ctgcn_wrecon_loss_f32(int64_t n, int64_t width, const float *Z, int64_t ldz, const int32_t *tgt, const int64_t *ent_ptr, int64_t entries,
+                          const int32_t *row_ptr, const int32_t *col, const float *val, double beta, const float *div, double scale,
+                          int32_t relu, float *dZ, int64_t lddz, float *loss, void *workspace, size_t workspace_bytes, void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
