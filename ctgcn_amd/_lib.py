@@ -213,6 +213,8 @@ SIGNATURES = {
     "ctgcn_wrecon_loss_workspace_bytes": (_sz, [_i64, _i64]),
     "ctgcn_wrecon_loss_f32": (_int, [_i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _c.c_double, _vp, _c.c_double, _i32, _vp, _i64, _vp, _vp,
                                      _sz, _vp]),
+    "ctgcn_lstm_cell_fwd_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "ctgcn_lstm_cell_bwd_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ctgcn_workspace_bytes": (_sz, [_int, _i64, _i64, _i32, _i32]),
 }
 

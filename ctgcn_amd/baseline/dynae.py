@@ -11,7 +11,8 @@ the device as one stacked CSR (ops.SnapshotRows) and a batch is a set of row ids
                   (β² (p_j − v_j)² − p_j²) at the target row's stored entries; no target or penalty tensor.
 A model takes a batch as a RowBatch or as (SnapshotRows, idx); a dense CUDA tensor goes through the reference's expressions in stock
 torch ops.  fused=False on the trainer runs that composed path end to end (dense rows and penalties made on the GPU): it is the
-comparand of the tests and of tools/dyngem_bench.py.
+comparand of the tests and of tools/dyngem_bench.py.  DynamicEmbedding, BatchGenerator, BatchPredictor and DynGraph2VecLoss also serve
+DynRNN and DynAERNN (dynrnn.py, dynaernn.py), whose batches are [B, look_back] row ids read step by step and not flattened.
 
 Reference behaviour that is reproduced because results depend on it:
   * learn_embedding makes a fresh generator for every batch, so every step trains on the first batch_size elements of a fresh shuffle
@@ -215,10 +216,14 @@ class DynGraph2VecLoss(nn.Module):
 
     def forward(self, model, input_list):
         """[x_reconstruct, x_real, y_penalty] as dense tensors (the reference's expression), or [z, batch] with z the decoder's
-        pre-activation [B, N] and batch the RowBatch it came from: the kernel path.  z is consumed: its memory receives the gradient."""
+        pre-activation [B, N] and batch the RowBatch it came from: the kernel path.  z is consumed: its memory receives the gradient.
+        A decoder that ends in an LSTM (DynRNN) hands over its prediction itself, the last h, which has no ReLU; ops.lstm_layer's
+        backward does not read that h, so it may be consumed too."""
         if len(input_list) == 2:
+            from .dynrnn import MLLSTM
             z, batch = input_list
-            reconstruct_loss = ops.wrecon_loss(z, batch.rows, batch.tgt, batch.beta, divide=False, scale=1.0 / z.shape[0], relu=True,
+            relu = not isinstance(getattr(model, 'decoder', None), MLLSTM)
+            reconstruct_loss = ops.wrecon_loss(z, batch.rows, batch.tgt, batch.beta, divide=False, scale=1.0 / z.shape[0], relu=relu,
                                                overwrite=True)
         else:
             assert len(input_list) == 3
@@ -283,13 +288,27 @@ class BatchPredictor:
         """(embedding [N, d], x_pred [N, N] or None) from the snapshots start .. of graph_list (all of them are the look_back inputs)"""
         rows = _as_rows(graph_list, next(model.parameters()).device)
         look_back = rows.T - start
+        name = getattr(model, 'method_name', 'DynAE')
         emb, pred = [], []
         with torch.no_grad():
-            first_t = model.encoder.first_transposed() if fused else None       # one transposed copy for all batches
+            if not fused:
+                first_t = None
+            elif name in ('DynRNN', 'DynAERNN'):
+                first_t = model.first_transposed()
+            else:
+                first_t = model.encoder.first_transposed()                      # one transposed copy for all batches
             for lo in range(0, self.node_num, self.batch_size):
                 nodes = np.arange(lo, min(self.node_num, lo + self.batch_size), dtype=np.int64)
                 idx = (start + np.arange(look_back, dtype=np.int64))[None, :] * rows.n + nodes[:, None]
-                if fused:
+                if name == 'DynRNN':                                            # the reconstruction comes from the sequence, not from hx
+                    seq, hx = model.encode((rows, idx), first_t) if fused else model.encoder(rows.dense(idx))
+                    emb.append(hx)
+                    if need_pred:
+                        pred.append(model.decode(seq) if fused else model.decoder(seq)[1])
+                    continue
+                if name == 'DynAERNN':
+                    hx = model.encode((rows, idx), first_t) if fused else model.rnn_encoder(model.ae_encoder(rows.dense(idx)))[1]
+                elif fused:
                     hx = model.encode((rows, idx), first_t)
                 else:
                     hx = model.encoder(rows.dense(idx).reshape(len(nodes), -1))
@@ -304,9 +323,10 @@ class DynamicEmbedding(object):
                  has_cuda=False):
         if not has_cuda:
             raise CtgcnHipError("DynamicEmbedding runs on the MI355X only (has_cuda=True); there is no CPU fallback")
-        from . import dyngem
-        if not isinstance(model, (DynAE, dyngem.DynGEM)):
-            raise NotImplementedError("DynamicEmbedding trains ctgcn_amd.baseline.DynGEM and ctgcn_amd.baseline.DynAE, got %s" % type(model).__name__)
+        from . import dynaernn, dyngem, dynrnn
+        if not isinstance(model, (DynAE, dyngem.DynGEM, dynrnn.DynRNN, dynaernn.DynAERNN)):
+            raise NotImplementedError("DynamicEmbedding trains ctgcn_amd.baseline.DynGEM and ctgcn_amd.baseline.DynAE, DynRNN and DynAERNN, got %s"
+                                      % type(model).__name__)
         self.base_path = base_path
         self.origin_base_path = os.path.abspath(os.path.join(base_path, origin_folder))
         self.embedding_base_path = os.path.abspath(os.path.join(base_path, embedding_folder))
@@ -359,8 +379,12 @@ class DynamicEmbedding(object):
             hx_j, xj_pred = model(xj_batch)
             return [xi_pred, xi_batch, yi_batch, xj_pred, xj_batch, yj_batch, hx_i, hx_j, value_batch]
         if fused:
+            if model.method_name == 'DynRNN':                              # the decoder reads the sequence; its last h is the prediction
+                return [model.decode(model.encode(batch)[0]), batch]
             return [model.decode(model.encode(batch), pre_activation=True), batch]
         x_pre_batches, x_cur_batch, y_batch = batch.dense()
+        if model.method_name != 'DynAE':                                   # DynAE alone takes the window flattened
+            x_pre_batches = x_pre_batches.view(x_pre_batches.shape[0], batch.idx.L, -1)
         _, x_pred_batch = model(x_pre_batches)
         return [x_pred_batch, x_cur_batch, y_batch]
 

@@ -3436,3 +3436,153 @@ def wrecon_loss(Z, rows, tgt, beta, divide=False, scale=1.0, relu=True, overwrit
     if Z.device != rows.device:
         raise ValueError("Z on %s but the snapshots on %s" % (Z.device, rows.device))
     return _WreconLoss.apply(_row_view(Z), rows, sel, float(beta), bool(divide), float(scale), bool(relu), bool(overwrite))
+
+
+# ------------------------------------------------------------------------- an LSTM layer of any width (ctgcn_lstmcell.hip): DynRNN, DynAERNN
+def _lstm_cell_fwd(gi_t, gh, bias, c_prev, h, c, gates):
+    lib = _lib.load()
+    B, H = c.shape
+    ld = lambda t: 0 if t is None else t.stride(0)  # noqa: E731
+    with torch.cuda.device(c.device), _timed("lstm_cell_fwd", n=B, d=H):
+        check(lib.ctgcn_lstm_cell_fwd_f32(B, H, ptr(gi_t), ld(gi_t), ptr(gh), ld(gh), ptr(bias), ptr(c_prev), ld(c_prev), ptr(h), ld(h), ptr(c),
+                                          ld(c), ptr(gates), ld(gates), _stream()), "ctgcn_lstm_cell_fwd_f32")
+
+
+def _lstm_cell_bwd(gates, c, c_prev, dh_out, dh_rec, dc_next, dgates, dc_prev):
+    lib = _lib.load()
+    B, H = c.shape
+    ld = lambda t: 0 if t is None else t.stride(0)  # noqa: E731
+    with torch.cuda.device(c.device), _timed("lstm_cell_bwd", n=B, d=H):
+        check(lib.ctgcn_lstm_cell_bwd_f32(B, H, ptr(gates), ld(gates), ptr(c), ld(c), ptr(c_prev), ld(c_prev), ptr(dh_out), ld(dh_out),
+                                          ptr(dh_rec), ld(dh_rec), ptr(dc_next), ld(dc_next), ptr(dgates), ld(dgates), ptr(dc_prev),
+                                          ld(dc_prev), _stream()), "ctgcn_lstm_cell_bwd_f32")
+
+
+def _time_major(t):
+    """a [B, L, D] tensor as a contiguous [L, B, D] one: a view where the memory already is (what lstm_layer returns), else a copy"""
+    tm = t.transpose(0, 1)
+    return tm if tm.is_contiguous() else tm.contiguous()
+
+
+class _LstmLayer(torch.autograd.Function):
+    """Every per-step tensor is time-major, [L, B, .]: a step is a contiguous [B, .] block for the GEMMs, and the steps >= 1 of dgates
+    and the steps < L - 1 of h are contiguous too, so dW_hh is one GEMM over them without a copy."""
+
+    @staticmethod
+    def forward(ctx, x, gi, w_ih, w_hh, b_ih, b_hh, last_only, train):
+        H = w_hh.shape[1]
+        dev = w_hh.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        own = gi is None
+        if own:
+            xt = _time_major(x)
+            L, B = xt.shape[:2]
+            x2d = xt.reshape(L * B, -1)
+            git = (torch.mm(x2d, w_ih.t()) if b_ih is None else torch.addmm(b_ih, x2d, w_ih.t())).view(L, B, 4 * H)
+        else:
+            xt = None
+            git = (gi if gi.stride(2) == 1 else gi.contiguous()).transpose(0, 1)
+            L, B = git.shape[:2]
+        gh = new(B, 4 * H) if L > 1 else None
+        w_hh_t = w_hh.t()
+        if train:
+            # the activated gates take the memory of a gi made here (a step's kernel reads and writes each element once)
+            gates = git if own else new(L, B, 4 * H)
+            c_all = new(L, B, H)
+            h_all = new(L - 1 if last_only else L, B, H)
+            h_last = new(B, H) if last_only else h_all[L - 1]
+            for t in range(L):
+                if t:
+                    torch.mm(h_all[t - 1], w_hh_t, out=gh)
+                _lstm_cell_fwd(git[t], gh if t else None, b_hh, c_all[t - 1] if t else None, h_last if t == L - 1 else h_all[t], c_all[t], gates[t])
+            ctx.save_for_backward(xt, w_ih, w_hh, gates, c_all, h_all)
+            ctx.own, ctx.last_only, ctx.has_bias = own, last_only, (b_ih is not None, b_hh is not None)
+        else:
+            c2 = new(2, B, H)
+            h_all = new(2 if last_only else L, B, H)
+            for t in range(L):
+                h_t = h_all[t & 1] if last_only else h_all[t]
+                if t:
+                    torch.mm(h_all[(t - 1) & 1] if last_only else h_all[t - 1], w_hh_t, out=gh)
+                _lstm_cell_fwd(git[t], gh if t else None, b_hh, c2[(t - 1) & 1] if t else None, h_t, c2[t & 1], None)
+            h_last = h_all[(L - 1) & 1] if last_only else None
+        return h_last if last_only else h_all.transpose(0, 1)
+
+    @staticmethod
+    def backward(ctx, dout):
+        xt, w_ih, w_hh, gates, c_all, h_all = ctx.saved_tensors
+        L, B, H4 = gates.shape
+        H = H4 // 4
+        dev = gates.device
+        if dout.dtype != torch.float32 or dout.stride(-1) != 1:
+            dout = dout.to(torch.float32).contiguous()
+        dgates = torch.empty(L, B, H4, dtype=torch.float32, device=dev)
+        dc = torch.empty(B, H, dtype=torch.float32, device=dev) if L > 1 else None
+        dh_rec = torch.empty(B, H, dtype=torch.float32, device=dev) if L > 1 else None
+        for t in range(L - 1, -1, -1):
+            last = t == L - 1
+            dh_out = (dout if last else None) if ctx.last_only else dout[:, t]
+            # dc is read as dc_next and written as dc_prev by the same thread
+            _lstm_cell_bwd(gates[t], c_all[t], c_all[t - 1] if t else None, dh_out, None if last else dh_rec, None if last else dc, dgates[t],
+                           dc if t else None)
+            if t:
+                torch.mm(dgates[t], w_hh, out=dh_rec)
+        need = ctx.needs_input_grad
+        dg2 = dgates.view(L * B, H4)
+        dx = dgi = dw_ih = dw_hh = db_ih = db_hh = None
+        if need[3]:
+            dw_hh = torch.mm(dgates[1:].reshape((L - 1) * B, H4).t(), h_all[:L - 1].reshape((L - 1) * B, H)) if L > 1 else torch.zeros_like(w_hh)
+        if (ctx.has_bias[0] and need[4]) or (ctx.has_bias[1] and need[5]):
+            db = dg2.sum(0)
+            db_ih = db if ctx.has_bias[0] and need[4] else None
+            db_hh = db if ctx.has_bias[1] and need[5] else None
+        if ctx.own:
+            x2d = xt.reshape(L * B, -1)
+            if need[2]:
+                dw_ih = torch.mm(dg2.t(), x2d)
+            if need[0]:
+                dx = torch.mm(dg2, w_ih).view(L, B, -1).transpose(0, 1)
+        elif need[1]:
+            dgi = dgates.transpose(0, 1)
+        return dx, dgi, dw_ih, dw_hh, db_ih, db_hh, None, None
+
+
+def lstm_layer(x, weight_ih, weight_hh, bias_ih=None, bias_hh=None, last_only=False, gi=None):
+    """One batch_first nn.LSTM layer of any hidden width H, zero initial state: h_seq [B, L, H], or with last_only only h_{L-1} [B, H].
+    x [B, L, in] is dense; or gi [B, L, 4 H] is the input projection made elsewhere (ops.rowsel_conv over adjacency rows, with bias_ih
+    folded by its maker; x, weight_ih and bias_ih are then None).  The parameters are those of the nn.LSTM (gate order i, f, g, o);
+    either bias may be None.  One library GEMM makes gi for all steps, one per step >= 1 makes h_{t-1} W_hhᵀ, and one
+    ctgcn_lstm_cell_fwd_f32 pass per step does the rest; the backward is one ctgcn_lstm_cell_bwd_f32 pass and one dgates_t W_hh GEMM per
+    step, then one GEMM each for dW_hh (over the stacked steps >= 1), dW_ih and dx, and one column sum for both bias gradients.  With
+    last_only the steps before the last get no gradient from above and no [B, L, H] zero tensor is made; h_{L-1} is a tensor of its own
+    which the backward never reads.  Without grad no gates are kept and c alternates between two buffers.  h_seq is a [B, L, H] view of
+    [L, B, H] memory, which a following lstm_layer takes as it is."""
+    _need_cuda(x, gi, weight_ih, weight_hh, bias_ih, bias_hh)
+    if (x is None) == (gi is None):
+        raise ValueError("exactly one of x and gi expected")
+    if gi is not None and (weight_ih is not None or bias_ih is not None):
+        raise ValueError("with gi, weight_ih and bias_ih belong to whoever made it")
+    for t in (x, gi, weight_ih, weight_hh, bias_ih, bias_hh):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("fp32 tensors expected, got %s" % t.dtype)
+    if weight_hh.dim() != 2 or weight_hh.shape[0] != 4 * weight_hh.shape[1] or weight_hh.shape[1] < 1:
+        raise ValueError("weight_hh must be [4 H, H]")
+    H = weight_hh.shape[1]
+    seq = x if gi is None else gi
+    if seq.dim() != 3 or seq.shape[1] < 1:
+        raise ValueError("%s must be [B, L, %s] with L >= 1" % (("x", "in") if gi is None else ("gi", "4 H")))
+    if gi is None:
+        if weight_ih is None or weight_ih.dim() != 2 or tuple(weight_ih.shape) != (4 * H, x.shape[2]):
+            raise ValueError("weight_ih must be [%d, %d]" % (4 * H, x.shape[2]))
+    elif gi.shape[2] != 4 * H:
+        raise ValueError("gi must be [B, L, %d], got %s" % (4 * H, tuple(gi.shape)))
+    for b in (bias_ih, bias_hh):
+        if b is not None and tuple(b.shape) != (4 * H,):
+            raise ValueError("a bias must be [%d]" % (4 * H))
+    for t in (seq, weight_ih, bias_ih, bias_hh):
+        if t is not None and t.device != weight_hh.device:
+            raise ValueError("tensors on %s and %s" % (t.device, weight_hh.device))
+    train = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, gi, weight_ih, weight_hh, bias_ih, bias_hh))
+    bias_hh = None if bias_hh is None else (bias_hh if bias_hh.is_contiguous() else bias_hh.contiguous())
+    return _LstmLayer.apply(x, gi, None if weight_ih is None else _row_view(weight_ih), _row_view(weight_hh), bias_ih, bias_hh, bool(last_only),
+                            train)

@@ -1173,6 +1173,30 @@ int ctgcn_wrecon_loss_f32(int64_t n, int64_t width, const float *Z, int64_t ldz,
                           const int32_t *row_ptr, const int32_t *col, const float *val, double beta, const float *div, double scale,
                           int32_t relu, float *dZ, int64_t lddz, float *loss, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- one time step of an LSTM layer of any width (ctgcn_lstmcell.hip; the DynRNN and DynAERNN baselines, reference baseline/dynRNN.py,
+ * baseline/dynAERNN.py).  The products with W_ih and W_hh are the caller's GEMMs; these are the element-wise passes between them.
+ * B rows of hidden width H; a gate operand is [B, 4 H] in torch's order i, f, g, o, a state operand [B, H]; every operand has its own
+ * row stride, so a step may be a slice of a [B, L, .] or [L, B, .] tensor.
+ * ctgcn_lstm_cell_fwd_f32: z = gi + gh + bias; i, f, o = σ(z), g = tanh(z); c = f c_prev + i g; h = o tanh(c).  gh null: no recurrent
+ *   term (step 0, h_{-1} = 0); bias [4 H] or null; c_prev null: zero.  Writes h, c and, unless gates is null (inference), the four
+ *   activated gates.  gates may be gi itself.
+ * ctgcn_lstm_cell_bwd_f32: from the saved activated gates, c of the step and c_prev (null at step 0: zero), with dh = dh_out + dh_rec
+ *   (the gradient from the layer above, and dgates_{t+1} W_hh from the caller's GEMM; either may be null) and dc = dh o (1 − tanh² c) +
+ *   dc_next (null: zero), writes the pre-activation gate gradients dgates = (dc g i (1 − i), dc c_prev f (1 − f), dc i (1 − g²),
+ *   dh tanh(c) o (1 − o)) and, unless dc_prev is null, dc_prev = dc f.  dc_prev may be dc_next itself; tanh(c) is recomputed.
+ * Every element of every operand is read once and written once.  16-byte accesses when H and every row stride are multiples of 4
+ * and every base is 16-byte aligned (the float4 rule of the gathers), scalar ones otherwise; 64-bit element indices; no atomics,
+ * repeated calls are bit-identical; σ and tanh are exact at saturation (0, 1, ±1 for |z| >= 100, never NaN).
+ * Returns CTGCN_E_INVALID for B outside [0, 2^31), H outside [1, 2^29), a row stride below the operand's width and a null gi, h, c
+ * (forward) or gates, c, dgates (backward); B = 0 returns CTGCN_OK before any pointer check.
+ */
+int ctgcn_lstm_cell_fwd_f32(int64_t B, int32_t H, const float *gi, int64_t ldgi, const float *gh, int64_t ldgh, const float *bias,
+                            const float *c_prev, int64_t ldcp, float *h, int64_t ldh, float *c, int64_t ldc, float *gates, int64_t ldg,
+                            void *stream);
+int ctgcn_lstm_cell_bwd_f32(int64_t B, int32_t H, const float *gates, int64_t ldg, const float *c, int64_t ldc, const float *c_prev,
+                            int64_t ldcp, const float *dh_out, int64_t lddo, const float *dh_rec, int64_t lddr, const float *dc_next,
+                            int64_t lddn, float *dgates, int64_t lddg, float *dc_prev, int64_t lddp, void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
