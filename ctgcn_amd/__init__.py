@@ -16,7 +16,7 @@ from .embedding import SupervisedEmbedding, UnsupervisedEmbedding  # noqa: F401
 from .baseline import (GAT, GCN, GCRN, GIN, PGNN, SAGE, Aggregator, EvolveGCN, GraphConvolution, Nonlinear, PGNN_layer,  # noqa: F401
                        SAGE_Layer, SpGraphAttentionLayer, VGRNN, GCNConv, InnerProductDecoder, graph_gru_gcn, BatchGenerator, BatchPredictor,
                        DynAE, DynamicEmbedding, DynGraph2VecLoss, RegularizationLoss, DynGEM, DynGEMBatchGenerator, DynGEMBatchPredictor,
-                       DynGEMLoss, DynRNN, DynAERNN, MLLSTM, MTMLP)
+                       DynGEMLoss, DynRNN, DynAERNN, MLLSTM, MTMLP, TIMERS, timers, timers_embedding)
 from .evaluation import DataGenerator, LinkPredictor, aggregate_results, evaluate, evaluate_window, link_prediction  # noqa: F401
 
 __all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoader", "NegativeSamplingLoss", "ReconstructionLoss",
@@ -25,4 +25,5 @@ __all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoade
            "GCN", "GraphConvolution", "GCRN", "GAT", "SpGraphAttentionLayer", "GIN", "SAGE", "SAGE_Layer", "Aggregator", "PGNN", "PGNN_layer", "Nonlinear",
            "VGRNN", "GCNConv", "graph_gru_gcn", "InnerProductDecoder", "VAELoss", "VAEClassificationLoss",
            "DynAE", "RegularizationLoss", "DynGraph2VecLoss", "BatchGenerator", "BatchPredictor", "DynamicEmbedding", "DynGEM", "DynGEMLoss",
-           "DynGEMBatchGenerator", "DynGEMBatchPredictor", "DynRNN", "DynAERNN", "MLLSTM", "MTMLP"]
+           "DynGEMBatchGenerator", "DynGEMBatchPredictor", "DynRNN", "DynAERNN", "MLLSTM", "MTMLP",
+           "TIMERS", "timers", "timers_embedding"]

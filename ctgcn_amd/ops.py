@@ -3586,3 +3586,198 @@ def lstm_layer(x, weight_ih, weight_hh, bias_ih=None, bias_hh=None, last_only=Fa
     bias_hh = None if bias_hh is None else (bias_hh if bias_hh.is_contiguous() else bias_hh.contiguous())
     return _LstmLayer.apply(x, gi, None if weight_ih is None else _row_view(weight_ih), _row_view(weight_hh), bias_ih, bias_hh, bool(last_only),
                             train)
+
+
+# ------------------------------------------------------------------------------------- fp64 blocks (ctgcn_timers.hip)
+def _f64_block(t, what):
+    if t.dtype != torch.float64 or t.dim() != 2:
+        raise TypeError("%s must be a 2-D fp64 tensor, got %s %s" % (what, t.dtype, tuple(t.shape)))
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def _f64_out(out, rows, cols, like, what):
+    if out is None:
+        return torch.empty(rows, cols, dtype=torch.float64, device=like.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (rows, cols) or out.stride(1) != 1 or out.stride(0) < cols or out.device != like.device:
+        raise ValueError("%s must be a [%d, %d] fp64 tensor with unit column stride on %s" % (what, rows, cols, like.device))
+    return out
+
+
+def _stored(t):
+    """t, or one zero of its kind for a matrix that stores nothing (an empty tensor has no address, and the entries are never read)"""
+    return t if t is None or t.numel() else t.new_zeros(1)
+
+
+def spmm_csr_f64(row_ptr, col, val, x, out=None, accumulate=False):
+    """Y = A·X (or Y += A·X into out) in fp64 on [n, b] blocks; x and out may be column slices of wider buffers."""
+    _need_cuda(row_ptr, col, val, x, out)
+    lib = _lib.load()
+    x = _f64_block(x, "x")
+    if val.dtype != torch.float64:
+        raise TypeError("fp64 values expected")
+    n, b = row_ptr.numel() - 1, x.shape[1]
+    if out is None:
+        accumulate = False
+    out = _f64_out(out, n, b, x, "out")
+    with torch.cuda.device(x.device):
+        check(lib.ctgcn_spmm_csr_f64(n, b, ptr(_i32(row_ptr)), ptr(_stored(_i32(col))), ptr(_stored(val.contiguous())), ptr(x), x.stride(0), ptr(out), out.stride(0),
+                                     1 if accumulate else 0, _stream()), "ctgcn_spmm_csr_f64")
+    return out
+
+
+def tsgemm_tn(x, y):
+    """G [b1, b2] = xᵀ·y over the n rows of two tall fp64 blocks (b1, b2 <= 512); fixed summation order."""
+    _need_cuda(x, y)
+    lib = _lib.load()
+    x, y = _f64_block(x, "x"), _f64_block(y, "y")
+    if x.shape[0] != y.shape[0]:
+        raise ValueError("x and y must have the same rows")
+    n, b1, b2 = x.shape[0], x.shape[1], y.shape[1]
+    G = torch.empty(b1, b2, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        nb = lib.ctgcn_tsgemm_tn_workspace_bytes(n, b1, b2)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=x.device)
+        check(lib.ctgcn_tsgemm_tn_f64(n, b1, b2, ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(G), ptr(ws), nb, _stream()), "ctgcn_tsgemm_tn_f64")
+    return G
+
+
+def tsgemm_nn(x, c, out=None, colsq=False):
+    """Y [n, b2] = x [n, b1]·c [b1, b2] in fp64 (b1 <= 1024, b2 <= 512); with colsq also the column sums of squares of Y: (Y, colsq)."""
+    _need_cuda(x, c, out)
+    lib = _lib.load()
+    x, c = _f64_block(x, "x"), _f64_block(c, "c")
+    if c.shape[0] != x.shape[1]:
+        raise ValueError("c must have x's columns as rows")
+    n, b1, b2 = x.shape[0], x.shape[1], c.shape[1]
+    out = _f64_out(out, n, b2, x, "out")
+    sq = torch.empty(b2, dtype=torch.float64, device=x.device) if colsq else None
+    with torch.cuda.device(x.device):
+        nb = lib.ctgcn_tsgemm_nn_workspace_bytes(n, b2) if colsq else 0
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=x.device) if colsq else None
+        check(lib.ctgcn_tsgemm_nn_f64(n, b1, b2, ptr(x), x.stride(0), ptr(c), c.stride(0), ptr(out), out.stride(0), ptr(sq), ptr(ws), nb,
+                                      _stream()), "ctgcn_tsgemm_nn_f64")
+    return (out, sq) if colsq else out
+
+
+def timers_obj(row_ptr, col, s, U, V, s_old=None):
+    """Device double[2] over the stored entries (r, c, s) of a CSR matrix, d = ⟨U_r, V_c⟩: (Σ s², Σ s·d), or with s_old (values on the
+    same pattern) (Σ (s_old + s − d)² − (s_old − d)², Σ s·d)."""
+    _need_cuda(row_ptr, col, s, U, V, s_old)
+    lib = _lib.load()
+    U, V = _f64_block(U, "U"), _f64_block(V, "V")
+    n, k = row_ptr.numel() - 1, U.shape[1]
+    if U.shape[0] != n or V.shape[1] != k:
+        raise ValueError("U must be [n, k] and V [., k]")
+    for t in (s, s_old):
+        if t is not None and (t.dtype != torch.float64 or t.numel() != col.numel()):
+            raise TypeError("one fp64 value per stored entry expected")
+    out = torch.zeros(2, dtype=torch.float64, device=U.device)
+    with torch.cuda.device(U.device):
+        nb = lib.ctgcn_timers_obj_workspace_bytes(n, k)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=U.device)
+        check(lib.ctgcn_timers_obj_f64(n, k, ptr(_i32(row_ptr)), ptr(_stored(_i32(col))), ptr(_stored(s.contiguous())),
+                                       ptr(None if s_old is None else _stored(s_old.contiguous())),
+                                       ptr(U), U.stride(0), ptr(V), V.stride(0), ptr(out), ptr(ws), nb, _stream()), "ctgcn_timers_obj_f64")
+    return out
+
+
+SYM_TOPK_DROP = 1e-7        # a direction of A·Q whose norm is below this fraction of the largest leaves the block
+
+
+def _chol_inverse_t(G):
+    """L⁻ᵀ of G = L Lᵀ (host, numpy), or None when G is not safely positive definite"""
+    import numpy as np
+    try:
+        L = np.linalg.cholesky((G + G.T) / 2)
+    except np.linalg.LinAlgError:
+        return None
+    d = np.diag(L)
+    if not np.all(np.isfinite(d)) or d.min() <= SYM_TOPK_DROP * d.max():
+        return None
+    return np.linalg.inv(L).T
+
+
+def _orthonormalise(Z, out_buf):
+    """CholeskyQR2 of the tall block Z into the leading columns of out_buf; returns the view.  Two passes of G = ZᵀZ = L Lᵀ (b x b,
+    on the host), Z ← Z L⁻ᵀ.  When the first G is not safely positive definite (A·Q has lost rank: an operator of rank below the block
+    width) the first pass uses G = V D Vᵀ instead and keeps the directions with √(D / D_max) above SYM_TOPK_DROP, so the block narrows
+    to the operator's numerical rank; an all-zero Z gives width 0."""
+    import numpy as np
+    dev = Z.device
+    G = tsgemm_tn(Z, Z).cpu().numpy()
+    C = _chol_inverse_t(G)
+    if C is None:
+        D, Vv = np.linalg.eigh((G + G.T) / 2)
+        keep = D > (SYM_TOPK_DROP ** 2) * max(D.max(), 0.0)
+        if not keep.any():
+            return out_buf[:, :0]
+        C = Vv[:, keep] / np.sqrt(D[keep])
+    Q1 = tsgemm_nn(Z, torch.from_numpy(np.ascontiguousarray(C)).to(dev))
+    C2 = _chol_inverse_t(tsgemm_tn(Q1, Q1).cpu().numpy())
+    if C2 is None:
+        raise RuntimeError("sym_topk: the second CholeskyQR pass met a Gram matrix that is not positive definite")
+    return tsgemm_nn(Q1, torch.from_numpy(np.ascontiguousarray(C2)).to(dev), out=out_buf[:, :C2.shape[0]])
+
+
+def sym_topk(apply, n, k, tol=1e-12, max_iter=5000, seed=0, device=None, _deficient_ok=False):
+    """The k eigenpairs of largest magnitude of a symmetric operator given as a callable on [n, b] fp64 device blocks (apply(Q) -> A·Q;
+    Q may be a column slice of a wider buffer): (w [k], X [n, k]) on the device, sorted by |w| descending, X orthonormal.
+
+    Block subspace iteration with Rayleigh–Ritz on a block of min(n, 2 k + 8) columns: Z = A·Q, H = QᵀZ, H = S Θ Sᵀ on the host, and
+    the residuals ‖A x − w x‖₂ of the k wanted Ritz pairs as the column norms of [Z | Q]·[S; −S Θ] (one ctgcn_tsgemm_nn_f64 with its
+    sums of squares); then Q ← CholeskyQR2(Z).  It stops when every wanted pair has ‖A x − w x‖₂ <= tol·|w₁| and raises a RuntimeError
+    naming the achieved residual after max_iter iterations: unconverged pairs are never returned.  Only b x b matrices and k-vectors
+    cross to the host inside the loop.  The start block is a seeded host generator's normal draws, so a seed gives the same block on
+    every run and device.  An operator of rank r < k has no k pairs this iteration can reach: RuntimeError.
+    sym_topk.last holds (iterations, largest residual) of the latest call."""
+    import numpy as np
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.CtgcnHipError("ctgcn_amd runs on MI355X only: sym_topk on %s; there is no CPU fallback." % device)
+    n, k = int(n), int(k)
+    if k < 1 or k > n:
+        raise ValueError("need 1 <= k <= n, got k=%d n=%d" % (k, n))
+    b = min(n, 2 * k + 8)
+    if b > 512:
+        raise ValueError("sym_topk: block width %d above 512 (k <= 252)" % b)
+    gen = torch.Generator().manual_seed(int(seed))
+    start = torch.randn(n, b, generator=gen, dtype=torch.float64).to(device)
+    W = torch.empty(n, 2 * b, dtype=torch.float64, device=device)          # [Z | Q], so that one product gives the residual block
+    Qbuf = torch.empty(n, b, dtype=torch.float64, device=device)
+    Q = _orthonormalise(start, Qbuf)
+    del start
+    res_max = float("inf")
+    for it in range(1, int(max_iter) + 1):
+        bw = Q.shape[1]
+        kk = min(k, bw)
+        if bw < k and not _deficient_ok:
+            raise RuntimeError("sym_topk: the operator has numerical rank %d, below the %d pairs asked for" % (bw, k))
+        if bw == 0:
+            break
+        Zv, Qv = W[:, :bw], W[:, bw:2 * bw]
+        Qv.copy_(Q)
+        Zv.copy_(apply(Qv))
+        H = tsgemm_tn(Qv, Zv).cpu().numpy()
+        theta, S = np.linalg.eigh((H + H.T) / 2)
+        order = np.argsort(-np.abs(theta), kind="stable")[:kk]
+        theta, S = theta[order], np.ascontiguousarray(S[:, order])
+        C = torch.from_numpy(np.concatenate((S, -S * theta[None, :]), axis=0)).to(device)
+        _, sq = tsgemm_nn(W[:, :2 * bw], C, colsq=True)
+        res_max = float(np.sqrt(sq.cpu().numpy().max()))
+        if res_max <= tol * abs(theta[0]):
+            X = torch.zeros(n, k, dtype=torch.float64, device=device)
+            tsgemm_nn(Qv, torch.from_numpy(S).to(device), out=X[:, :kk])
+            w = torch.zeros(k, dtype=torch.float64, device=device)
+            w[:kk] = torch.from_numpy(theta).to(device)
+            sym_topk.last = (it, res_max)
+            return w, X
+        Q = _orthonormalise(Zv, Qbuf)
+    else:
+        raise RuntimeError("sym_topk: residual %.3e after %d iterations, above tol·|w1| = %.3e" % (res_max, max_iter, tol * abs(theta[0])))
+    sym_topk.last = (it, 0.0)          # a zero operator (only with _deficient_ok): zero pairs
+    return torch.zeros(k, dtype=torch.float64, device=device), torch.zeros(n, k, dtype=torch.float64, device=device)
+
+
+sym_topk.last = (0, 0.0)

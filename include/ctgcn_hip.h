@@ -1197,6 +1197,36 @@ int ctgcn_lstm_cell_bwd_f32(int64_t B, int32_t H, const float *gates, int64_t ld
                             int64_t ldcp, const float *dh_out, int64_t lddo, const float *dh_rec, int64_t lddr, const float *dc_next,
                             int64_t lddn, float *dgates, int64_t lddg, float *dc_prev, int64_t lddp, void *stream);
 
+/* ---- the fp64 linear algebra of the TIMERS baseline (ctgcn_timers.hip; reference baseline/timers.py): the passes of a block
+ * eigensolver on a CSR operator (ops.sym_topk), the edge-gather loss, TRIP and the restart bound.  Everything is double, row-major
+ * with leading dimensions in elements; CSR as in ctgcn_spmm_csr_f32 (int32 row_ptr[n + 1] and col).
+ * ctgcn_spmm_csr_f64: Y[n, b] = A·X, or Y += A·X with accumulate != 0; each row's sum in CSR order.  Y must not overlap X.
+ * ctgcn_tsgemm_tn_f64: G[b1, b2] (dense, row stride b2) = Xᵀ·Y over n rows, X [n, b1], Y [n, b2] (Y may be X).  n = 0 zeroes G.
+ *   workspace: ctgcn_tsgemm_tn_workspace_bytes (0 up to 512 rows: one run, no partials).
+ * ctgcn_tsgemm_nn_f64: Y[n, b2] = X[n, b1]·C[b1, b2]; colsq (device double[b2], or null) = the column sums of squares of Y.  Y must
+ *   not overlap X.  workspace: ctgcn_tsgemm_nn_workspace_bytes, read only with colsq.
+ * ctgcn_timers_obj_f64: over the stored entries (r, c, s) of a CSR matrix, with d = ⟨U_r, V_c⟩ over k columns: out[0] = Σ s² and
+ *   out[1] = Σ s·d; with s_old (a second value array on the same pattern) out[0] = Σ (s_old + s − d)² − (s_old − d)² instead.
+ *   workspace: ctgcn_timers_obj_workspace_bytes.
+ * Limits: 1 <= b1, b2 <= 512 in the two products (b1 <= 1024 in ctgcn_tsgemm_nn_f64, whose X may be two blocks side by side), else
+ * CTGCN_E_UNSUPPORTED; n < 2^31 in the two CSR passes.
+ * Returns CTGCN_E_INVALID for bad sizes, a leading dimension below its width and null pointers, CTGCN_E_WORKSPACE for a workspace
+ * that is too small; n = 0 returns CTGCN_OK before any pointer check.  No float atomics: per-block partials summed in a fixed order,
+ * their count a function of the sizes alone, so repeated calls are bit-identical.
+ */
+int ctgcn_spmm_csr_f64(int64_t n_rows, int32_t b, const int32_t *row_ptr, const int32_t *col_idx, const double *val, const double *X,
+                       int64_t ldx, double *Y, int64_t ldy, int accumulate, void *stream);
+size_t ctgcn_tsgemm_tn_workspace_bytes(int64_t n, int32_t b1, int32_t b2);
+int ctgcn_tsgemm_tn_f64(int64_t n, int32_t b1, int32_t b2, const double *X, int64_t ldx, const double *Y, int64_t ldy, double *G,
+                        void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_tsgemm_nn_workspace_bytes(int64_t n, int32_t b2);
+int ctgcn_tsgemm_nn_f64(int64_t n, int32_t b1, int32_t b2, const double *X, int64_t ldx, const double *C, int64_t ldc, double *Y,
+                        int64_t ldy, double *colsq, void *workspace, size_t workspace_bytes, void *stream);
+size_t ctgcn_timers_obj_workspace_bytes(int64_t n, int32_t k);
+int ctgcn_timers_obj_f64(int64_t n, int32_t k, const int32_t *row_ptr, const int32_t *col, const double *s, const double *s_old,
+                         const double *U, int64_t ldu, const double *V, int64_t ldv, double *out, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 size_t ctgcn_workspace_bytes(int op, int64_t n, int64_t nnz, int32_t d, int32_t K);
 
 #ifdef __cplusplus
