@@ -16,7 +16,8 @@ from .embedding import SupervisedEmbedding, UnsupervisedEmbedding  # noqa: F401
 from .baseline import (GAT, GCN, GCRN, GIN, PGNN, SAGE, Aggregator, EvolveGCN, GraphConvolution, Nonlinear, PGNN_layer,  # noqa: F401
                        SAGE_Layer, SpGraphAttentionLayer, VGRNN, GCNConv, InnerProductDecoder, graph_gru_gcn, BatchGenerator, BatchPredictor,
                        DynAE, DynamicEmbedding, DynGraph2VecLoss, RegularizationLoss, DynGEM, DynGEMBatchGenerator, DynGEMBatchPredictor,
-                       DynGEMLoss, DynRNN, DynAERNN, MLLSTM, MTMLP, TIMERS, timers, timers_embedding)
+                       DynGEMLoss, DynRNN, DynAERNN, MLLSTM, MTMLP, TIMERS, timers, timers_embedding, TgGAT, TgGATConv, TgGCN, TgGCNConv, TgGIN,
+                       TgGINConv, TgSAGE, TgSAGEConv)
 from .evaluation import DataGenerator, LinkPredictor, aggregate_results, evaluate, evaluate_window, link_prediction  # noqa: F401
 
 __all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoader", "NegativeSamplingLoss", "ReconstructionLoss",
@@ -26,4 +27,5 @@ __all__ = ["CoreAdj", "CoreDiffusion", "MLP", "CDN", "CGCN", "CTGCN", "DataLoade
            "VGRNN", "GCNConv", "graph_gru_gcn", "InnerProductDecoder", "VAELoss", "VAEClassificationLoss",
            "DynAE", "RegularizationLoss", "DynGraph2VecLoss", "BatchGenerator", "BatchPredictor", "DynamicEmbedding", "DynGEM", "DynGEMLoss",
            "DynGEMBatchGenerator", "DynGEMBatchPredictor", "DynRNN", "DynAERNN", "MLLSTM", "MTMLP",
-           "TIMERS", "timers", "timers_embedding"]
+           "TIMERS", "timers", "timers_embedding",
+           "TgGCN", "TgGAT", "TgSAGE", "TgGIN", "TgGCNConv", "TgGATConv", "TgSAGEConv", "TgGINConv"]

@@ -172,6 +172,19 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "ctgcn_gat_bwd_col_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _c.c_double, _c.c_double, _c.c_uint64,
                                      _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_tg_keys": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ctgcn_tg_csr_count": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ctgcn_tg_csr_emit": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctgcn_tg_conv_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _i64, _i32, _c.c_double, _c.c_uint64,
+                                     _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_tg_prep_workspace_bytes": (_sz, [_i64, _i32]),
+    "ctgcn_tg_conv_prep_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _c.c_double, _c.c_uint64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ctgcn_tgat_fwd_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _c.c_double, _vp, _i32, _c.c_double, _c.c_uint64, _vp, _i64,
+                                  _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_tgat_bwd_row_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _c.c_double, _vp, _i64, _vp, _vp,
+                                      _vp, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_tgat_bwd_col_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _c.c_double, _vp, _vp, _i64, _vp,
+                                      _i64, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "ctgcn_pool_conv_fwd_f32": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _i64, _i32, _c.c_double, _c.c_uint64,
                                        _vp, _vp, _i64, _vp, _i32, _i32, _vp, _sz, _vp]),
     "ctgcn_pool_prep_workspace_bytes": (_sz, [_i64, _i32]),

@@ -11,5 +11,6 @@ from .gin import GIN  # noqa: F401
 from .pgnn import (PGNN, Nonlinear, PGNN_layer, anchor_set_count, get_dist_max, get_random_anchorset,  # noqa: F401
                    precompute_dist_data, preselect_anchor)
 from .sage import SAGE, SAGE_Layer, Aggregator  # noqa: F401
+from .tg import TgGAT, TgGATConv, TgGCN, TgGCNConv, TgGIN, TgGINConv, TgSAGE, TgSAGEConv  # noqa: F401
 from .timers import TIMERS, timers, timers_embedding  # noqa: F401
 from .vgrnn import VGRNN, GCNConv, InnerProductDecoder, LazyInnerProduct, gcn_conv_adjacency, graph_gru_gcn  # noqa: F401

@@ -20,6 +20,10 @@
 // work: the sums over entries are linear in it, so one dot product per (row, head) on the finished sums replaces one per entry.
 // No atomics; every sum has a fixed order, so repeated launches are bit-identical.  Nothing of nnz x F elements exists, and no
 // per-entry array at all: p_ij and the dropout draw are recomputed from u, v, m, Z and (key + h, i, j) in each pass.
+//
+// The same passes serve PyG's GATConv (ctgcn_tgat_*; TgGAT in ctgcn_amd/baseline/tg.py) with lsign = +1: l_ij = +leakyrelu(z_ij), so
+// m_i = leakyrelu(u_i + max_j v_j), dz_ij = +s_ij dl_ij and du, dv change sign; the forward adds a bias and its epilogue is ReLU and
+// dropout; there is no attention dropout.  With lsign = -1 every expression below reduces to the reference form's bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -34,6 +38,7 @@ namespace {
 constexpr int U = 4;                   // gathered rows in flight per lane group
 constexpr int FWD = 0, ROW = 1, COL = 2;
 constexpr int EPI_NONE = 0, EPI_ELU = 1, EPI_ELU_DROP = 2;
+constexpr int EPI_RELU = 3;               // the PyG form's ReLU and dropout (ctgcn_tgat_fwd_f32 alone; the reference-form entry points refuse it)
 constexpr int MIN_LANES = 16;          // lanes per row of the row-maximum pre-pass
 
 struct GatArgs {
@@ -47,7 +52,10 @@ struct GatArgs {
     const float *v;         // [n, heads]: of the gathered row (FWD, ROW), of the own row (COL)
     const float *m;         // FWD: [n, heads]
     const f4 *pack;         // ROW: of the own row, COL: of the gathered row: {u, m, 1 / Z (0 for an empty row), D} [n, heads]
+    const float *ctr;       // ROW, PyG form: Y [n, d], the row's own output, taken off every gathered row (see add_entry); else null
+    int64_t ldctr;
     float alpha;
+    float lsign;            // l = lsign leakyrelu(z): -1 the reference's layer, +1 PyG's GATConv
     int32_t drop;           // p_att > 0
     double p_att;
     float att_scale;        // 1 / (1 - p_att)
@@ -57,6 +65,7 @@ struct GatArgs {
     float *out2;            // FWD: Y before the epilogue (null without one); COL: B
     int64_t ld2;
     float *sout;            // [n, heads]  FWD: Z; ROW: c; COL: k
+    const float *bias;      // FWD, PyG form: [d] added to Y before the epilogue, or null
     int32_t epi, fdrop;     // FWD: the epilogue; p_feat > 0
     double p_feat;
     float fscale;
@@ -74,6 +83,7 @@ struct GatArgs {
 struct Own {
     float a;                // u_i (FWD, ROW) or v_j (COL)
     float m, iz;            // FWD: m_i; ROW: m_i, 1 / Z_i
+    float s0;               // ROW: a slope taken off every s_ij of the row (see add_entry); 0 in the reference form
     uint64_t key;           // key + h
 };
 
@@ -82,8 +92,13 @@ __device__ __forceinline__ Own own_of(const GatArgs &a, int64_t row, int h)
 {
     Own o;
     const int64_t k = row * a.heads + h;
+    o.s0 = 0.f;
     if (MODE == FWD) { o.a = a.u[k]; o.m = a.m[k]; o.iz = 0.f; }
-    else if (MODE == ROW) { const f4 p = a.pack[k]; o.a = p.x; o.m = p.y; o.iz = p.z; }
+    else if (MODE == ROW) {
+        const f4 p = a.pack[k];
+        o.a = p.x; o.m = p.y; o.iz = p.z;
+        if (a.lsign > 0.f) o.s0 = p.y > 0.f ? 1.f : a.alpha;       // PyG form: the slope at the row's largest logit (m = leakyrelu(z_max))
+    }
     else { o.a = a.v[k]; o.m = 0.f; o.iz = 0.f; }
     o.key = a.key + (uint64_t)h;
     return o;
@@ -103,7 +118,7 @@ __device__ __forceinline__ void add_entry(const GatArgs &a, const Own &o, int64_
 {
     const float z = MODE == COL ? side.x + o.a : o.a + side.x;
     const bool pos = z > 0.f;
-    const float l = -(pos ? z : a.alpha * z);
+    const float l = a.lsign * (pos ? z : a.alpha * z);
     float q = 1.f;
     if (a.drop) {
         const double r = MODE == COL ? ctgcn_u01(o.key, (uint64_t)c, (uint64_t)row) : ctgcn_u01(o.key, (uint64_t)row, (uint64_t)c);
@@ -114,9 +129,14 @@ __device__ __forceinline__ void add_entry(const GatArgs &a, const Own &o, int64_
         s += e;
         A1 = vfma(q * e, x, A1);
     } else if (MODE == ROW) {
-        const float sp = (pos ? 1.f : a.alpha) * (expf(l - o.m) * o.iz);
-        s += sp;
-        A1 = vfma(sp * q, x, A1);
+        // du_i = sum_j s_ij p_ij (t_ij - D_i) and sum_j p_ij (t_ij - D_i) = 0: any slope s0 constant over the row may be taken off
+        // s_ij.  With s0 the slope at the largest logit, a row whose logits lie on one side of 0 gives du_i = 0 exactly, where
+        // G·R - D c would leave the rounding of two equal sums (all of att_r's gradient when every row is like that).
+        // With a.ctr, A2 holds Y_i and R_i = sum_j w_ij (S_j - Y_i): t_ij - D_i = G_i · (S_j - Y_i) without attention dropout, so
+        // du_i = G_i · R_i with c_i left at 0, and what the S_j have in common (a bias of the layer before) never enters the sum.
+        const float sp = ((pos ? 1.f : a.alpha) - o.s0) * (expf(l - o.m) * o.iz);
+        if (!a.ctr) s += sp;
+        A1 = vfma(sp * q, x - A2, A1);                            // A2 = 0 in the reference form
     } else {
         const float p = expf(l - side.y) * side.z;
         const float sl = pos ? 1.f : a.alpha;
@@ -171,7 +191,19 @@ __device__ __forceinline__ void finish(const GatArgs &a, int64_t row, int h, int
         V y = V(0.f);
         if (s > 0.f) y = A1 / s;                                  // an empty row: exact zeros
         V o = y;
-        if (a.epi != EPI_NONE) {
+        if (a.epi == EPI_RELU || a.bias) {                        // PyG form: the bias, then ReLU and dropout
+            float *po = (float *)&o;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                float t = a.bias ? po[k] + a.bias[foff + k] : po[k];
+                if (a.epi == EPI_RELU) {
+                    t = t > 0.f ? t : 0.f;
+                    if (a.fdrop) t = ctgcn_u01(a.fkey, (uint64_t)row, (uint64_t)(foff + k)) >= a.p_feat ? t * a.fscale : 0.f;
+                }
+                po[k] = t;
+            }
+            *(V *)(a.out2 + row * a.ld2 + foff) = y;
+        } else if (a.epi != EPI_NONE) {
             float *po = (float *)&o;
             const float *py = (const float *)&y;
 #pragma unroll
@@ -209,6 +241,7 @@ __global__ __launch_bounds__(256) void gat_row_kernel(const GatArgs a)
         const Own o = own_of<MODE>(a, row, h);
         V A1 = V(0.f), A2 = V(0.f);
         float s = 0.f;
+        if (MODE == ROW && a.ctr) A2 = *(const V *)(a.ctr + row * a.ldctr + foff);
         row_sum<VEC, LPR, MODE>(a, o, row, h, start, end, lig, foff, A1, A2, s);
         if (live) finish<VEC, MODE>(a, row, h, foff, A1, A2, s);
     }
@@ -241,6 +274,7 @@ __global__ __launch_bounds__(PIECE_THREADS) void gat_piece_kernel(const GatArgs 
         const Own o = own_of<MODE>(a, row, h);
         V A1 = V(0.f), A2 = V(0.f);
         float s = 0.f;
+        if (MODE == ROW && a.ctr) A2 = *(const V *)(a.ctr + row * a.ldctr + foff);
         for (int e = lo + g; e < hi; e += PIECE_GROUPS) {
             const int c = a.col[e];
             add_entry<MODE, V>(a, o, row, c, side_of<MODE>(a, c, h), *(const V *)(a.src + (int64_t)c * a.ldsrc + foff), A1, A2, s);
@@ -288,15 +322,16 @@ __global__ __launch_bounds__(64) void gat_final_kernel(const GatArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ the row maximum m
-// m[i][h] = -leakyrelu(u[i][h] + min_j v[col_j][h]) (0 for an empty row); MIN_LANES lanes per row, a block per long row
-__device__ __forceinline__ float shift_of(float u, float vmin, float alpha)
+// m[i][h] = -leakyrelu(u[i][h] + min_j v[col_j][h]) (0 for an empty row); MIN_LANES lanes per row, a block per long row.  With
+// lsign = +1 the logit increases in v: the minimum is taken of -v and m = leakyrelu(u + max_j v).
+__device__ __forceinline__ float shift_of(float u, float vmin, float alpha, float lsign)
 {
-    const float z = u + vmin;
-    return -(z > 0.f ? z : alpha * z);
+    const float z = u - lsign * vmin;
+    return lsign * (z > 0.f ? z : alpha * z);
 }
 
 __global__ __launch_bounds__(256) void gat_rowmax_kernel(int64_t n, int32_t heads, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
-                                                         const float *__restrict__ u, const float *__restrict__ v, float alpha,
+                                                         const float *__restrict__ u, const float *__restrict__ v, float alpha, float lsign,
                                                          float *__restrict__ m, int32_t n_long, int32_t long_thresh)
 {
     const int lig = threadIdx.x & (MIN_LANES - 1);
@@ -306,15 +341,15 @@ __global__ __launch_bounds__(256) void gat_rowmax_kernel(int64_t n, int32_t head
     if (n_long > 0 && end - start > long_thresh) return;
     for (int h = 0; h < heads; ++h) {
         float mn = INFINITY;
-        for (int e = start + lig; e < end; e += MIN_LANES) mn = fminf(mn, v[(int64_t)col[e] * heads + h]);
+        for (int e = start + lig; e < end; e += MIN_LANES) mn = fminf(mn, -lsign * v[(int64_t)col[e] * heads + h]);
 #pragma unroll
         for (int o = MIN_LANES / 2; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o, MIN_LANES));
-        if (lig == 0) m[row * heads + h] = end > start ? shift_of(u[row * heads + h], mn, alpha) : 0.f;
+        if (lig == 0) m[row * heads + h] = end > start ? shift_of(u[row * heads + h], mn, alpha, lsign) : 0.f;
     }
 }
 
 __global__ __launch_bounds__(256) void gat_rowmax_long_kernel(int32_t heads, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
-                                                              const float *__restrict__ u, const float *__restrict__ v, float alpha,
+                                                              const float *__restrict__ u, const float *__restrict__ v, float alpha, float lsign,
                                                               float *__restrict__ m, const int32_t *__restrict__ long_rows)
 {
     __shared__ float sm[4];
@@ -322,12 +357,12 @@ __global__ __launch_bounds__(256) void gat_rowmax_long_kernel(int32_t heads, con
     const int start = row_ptr[row], end = row_ptr[row + 1];
     for (int h = 0; h < heads; ++h) {
         float mn = INFINITY;
-        for (int e = start + threadIdx.x; e < end; e += 256) mn = fminf(mn, v[(int64_t)col[e] * heads + h]);
+        for (int e = start + threadIdx.x; e < end; e += 256) mn = fminf(mn, -lsign * v[(int64_t)col[e] * heads + h]);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o, 64));
         if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = mn;
         __syncthreads();
-        if (threadIdx.x == 0) m[row * heads + h] = shift_of(u[row * heads + h], fminf(fminf(sm[0], sm[1]), fminf(sm[2], sm[3])), alpha);
+        if (threadIdx.x == 0) m[row * heads + h] = shift_of(u[row * heads + h], fminf(fminf(sm[0], sm[1]), fminf(sm[2], sm[3])), alpha, lsign);
         __syncthreads();
     }
 }
@@ -355,6 +390,7 @@ struct PairArgs {
     double p_feat;
     float fscale;
     uint64_t fkey;
+    float dsign;            // DU, FINISH: dz / dl's sign, +1 the reference's layer (dz = -s dl is in the formulas), -1 PyG's
 };
 
 template <int KIND>
@@ -398,9 +434,9 @@ __global__ __launch_bounds__(256) void gat_pair_kernel(const PairArgs a)
     } else if (KIND == PREP) {
         if (l == 0) { const float Z = a.s3[pair]; a.pack[pair] = f4{a.s1[pair], a.s2[pair], Z > 0.f ? 1.f / Z : 0.f, t1}; }
     } else if (KIND == DU) {
-        if (l == 0) a.o1[pair] = fmaf(a.pack[pair].w, a.s1[pair], -t1);
+        if (l == 0) a.o1[pair] = a.dsign * fmaf(a.pack[pair].w, a.s1[pair], -t1);
     } else {
-        const float dv = a.s1[pair] - t1;
+        const float dv = a.dsign * (a.s1[pair] - t1);
         if (l == 0) a.o1[pair] = dv;
         if (a.G) {
             const float du = a.s2[pair];
@@ -535,6 +571,46 @@ bool bad_scalars(const char *what, double alpha, double p_att, double p_feat, in
     return rc != CTGCN_OK;
 }
 
+// The three gathers behind the reference-form entry points (lsign -1, no bias) and the PyG-form ones (lsign +1).  The PyG form has no
+// attention dropout; its epi is 0 or 1 (ReLU, then dropout when p_feat > 0), and Y is written whenever out differs from it.
+int fwd_impl(const char *what, float lsign, int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S,
+             int64_t lds, const float *a_src, const float *a_dst, double alpha, const float *bias, int32_t epi, double p_att, uint64_t key,
+             double p_feat, uint64_t fkey, float *out, int64_t ldout, float *Y, int64_t ldy, float *u, float *v, float *m, float *Z,
+             const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const bool pyg = lsign > 0.f;
+    int rc = check_shape(what, n, d, heads);
+    if (rc < 0) return rc;
+    if (pyg) {
+        if (bad_scalars(what, alpha, 0.0, p_feat, EPI_NONE, rc)) return rc;
+        if (epi != 0 && epi != 1) return ctgcn_fail(CTGCN_E_INVALID, what, "epi must be 0 (none) or 1 (ReLU, dropout)");
+        epi = epi ? EPI_RELU : EPI_NONE;
+    } else if (bad_scalars(what, alpha, p_att, p_feat, epi, rc)) return rc;
+    const bool keep_y = epi != EPI_NONE || bias;
+    if (lds < d || ldout < d || (keep_y && ldy < d)) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (n == 0) return CTGCN_OK;
+    if (!S || !a_src || !a_dst || !out || !u || !v || !m || !Z || (keep_y && !Y)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    GatArgs a{};
+    if ((rc = set_gather(a, what, n, d, heads, row_ptr, col, alpha, p_att, key, long_rows, n_long, long_threshold, workspace, workspace_bytes))) return rc;
+    a.lsign = lsign; a.bias = bias;
+    hipStream_t st = (hipStream_t)stream;
+    PairArgs s{};
+    s.heads = heads; s.F = a.F; s.X = S; s.ldx = lds; s.a_src = a_src; s.a_dst = a_dst; s.o1 = u; s.o2 = v;
+    if ((rc = launch_pairs<SCORES>(s, n, st))) return rc;
+    hipLaunchKernelGGL(gat_rowmax_kernel, dim3((unsigned)((n + 256 / MIN_LANES - 1) / (256 / MIN_LANES))), dim3(256), 0, st, n, heads, row_ptr, col,
+                       (const float *)u, (const float *)v, a.alpha, lsign, m, n_long, long_threshold);
+    CTGCN_TRY(hipGetLastError());
+    if (n_long > 0) {
+        hipLaunchKernelGGL(gat_rowmax_long_kernel, dim3((unsigned)n_long), dim3(256), 0, st, heads, row_ptr, col, (const float *)u, (const float *)v,
+                           a.alpha, lsign, m, long_rows);
+        CTGCN_TRY(hipGetLastError());
+    }
+    a.src = S; a.ldsrc = lds; a.u = u; a.v = v; a.m = m;
+    a.out1 = out; a.ld1 = ldout; a.out2 = keep_y ? Y : nullptr; a.ld2 = ldy; a.sout = Z;
+    a.epi = epi; a.fdrop = (epi == EPI_ELU_DROP || epi == EPI_RELU) && p_feat > 0.0; a.p_feat = p_feat; a.fscale = 1.0f / (1.0f - (float)p_feat); a.fkey = fkey;
+    return dispatch<FWD>(a, float4_rows(a.F, {{S, lds}, {out, ldout}, {a.out2, ldy}}), stream);
+}
+
 }  // namespace
 
 extern "C" int32_t ctgcn_gat_piece_floats(int32_t d, int32_t heads) { return (d < 1 || heads < 1) ? 0 : piece_floats(d, heads); }
@@ -545,31 +621,18 @@ extern "C" int ctgcn_gat_fwd_f32(int64_t n, int32_t d, int32_t heads, const int3
                                  const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
                                  void *stream)
 {
-    const char *what = "gat_fwd";
-    int rc = check_shape(what, n, d, heads);
-    if (rc < 0) return rc;
-    if (bad_scalars(what, alpha, p_att, p_feat, epi, rc)) return rc;
-    if (lds < d || ldout < d || (epi != EPI_NONE && ldy < d)) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
-    if (n == 0) return CTGCN_OK;
-    if (!S || !a_src || !a_dst || !out || !u || !v || !m || !Z || (epi != EPI_NONE && !Y)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
-    GatArgs a{};
-    if ((rc = set_gather(a, what, n, d, heads, row_ptr, col, alpha, p_att, key, long_rows, n_long, long_threshold, workspace, workspace_bytes))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    PairArgs s{};
-    s.heads = heads; s.F = a.F; s.X = S; s.ldx = lds; s.a_src = a_src; s.a_dst = a_dst; s.o1 = u; s.o2 = v;
-    if ((rc = launch_pairs<SCORES>(s, n, st))) return rc;
-    hipLaunchKernelGGL(gat_rowmax_kernel, dim3((unsigned)((n + 256 / MIN_LANES - 1) / (256 / MIN_LANES))), dim3(256), 0, st, n, heads, row_ptr, col,
-                       (const float *)u, (const float *)v, a.alpha, m, n_long, long_threshold);
-    CTGCN_TRY(hipGetLastError());
-    if (n_long > 0) {
-        hipLaunchKernelGGL(gat_rowmax_long_kernel, dim3((unsigned)n_long), dim3(256), 0, st, heads, row_ptr, col, (const float *)u, (const float *)v,
-                           a.alpha, m, long_rows);
-        CTGCN_TRY(hipGetLastError());
-    }
-    a.src = S; a.ldsrc = lds; a.u = u; a.v = v; a.m = m;
-    a.out1 = out; a.ld1 = ldout; a.out2 = epi != EPI_NONE ? Y : nullptr; a.ld2 = ldy; a.sout = Z;
-    a.epi = epi; a.fdrop = epi == EPI_ELU_DROP && p_feat > 0.0; a.p_feat = p_feat; a.fscale = 1.0f / (1.0f - (float)p_feat); a.fkey = fkey;
-    return dispatch<FWD>(a, float4_rows(a.F, {{S, lds}, {out, ldout}, {a.out2, ldy}}), stream);
+    return fwd_impl("gat_fwd", -1.f, n, d, heads, row_ptr, col, S, lds, a_src, a_dst, alpha, nullptr, epi, p_att, key, p_feat, fkey, out, ldout, Y, ldy,
+                    u, v, m, Z, long_rows, n_long, long_threshold, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ctgcn_tgat_fwd_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S, int64_t lds,
+                                  const float *a_tgt, const float *a_src, double slope, const float *bias, int32_t epi, double p, uint64_t key,
+                                  float *out, int64_t ldout, float *Y, int64_t ldy, float *u, float *v, float *m, float *Z,
+                                  const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
+                                  void *stream)
+{
+    return fwd_impl("tgat_fwd", 1.f, n, d, heads, row_ptr, col, S, lds, a_tgt, a_src, slope, bias, epi, 0.0, 0, p, key, out, ldout, Y, ldy, u, v, m, Z,
+                    long_rows, n_long, long_threshold, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ctgcn_gat_bwd_prep_f32(int64_t n, int32_t d, int32_t heads, const float *dY, int64_t lddy, const float *Y, int64_t ldy, int32_t epi,
@@ -591,35 +654,36 @@ extern "C" int ctgcn_gat_bwd_prep_f32(int64_t n, int32_t d, int32_t heads, const
     return launch_pairs<PREP>(s, n, (hipStream_t)stream);
 }
 
-extern "C" int ctgcn_gat_bwd_row_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S, int64_t lds,
-                                     const float *G, int64_t ldg, const float *v, const void *pack, double alpha, double p_att, uint64_t key,
-                                     float *R, int64_t ldr, float *csum, float *du, const int32_t *long_rows, int32_t n_long,
-                                     int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream)
+namespace {
+
+int bwd_row_impl(const char *what, float lsign, int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S,
+                 int64_t lds, const float *G, int64_t ldg, const float *Y, int64_t ldy, const float *v, const void *pack, double alpha,
+                 double p_att, uint64_t key, float *R, int64_t ldr, float *csum, float *du, const int32_t *long_rows, int32_t n_long,
+                 int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const char *what = "gat_bwd_row";
+    const bool pyg = lsign > 0.f;                                 // Y: the PyG form's centre of the gathered rows; null in the reference form
     int rc = check_shape(what, n, d, heads);
     if (rc < 0) return rc;
     if (bad_scalars(what, alpha, p_att, 0.0, EPI_NONE, rc)) return rc;
-    if (lds < d || ldg < d || ldr < d) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
+    if (lds < d || ldg < d || ldr < d || (pyg && ldy < d)) return ctgcn_fail(CTGCN_E_INVALID, what, "leading dimension below d");
     if (n == 0) return CTGCN_OK;
-    if (!S || !G || !v || !pack || !R || !csum || !du) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
+    if (!S || !G || !v || !pack || !R || !csum || !du || (pyg && !Y)) return ctgcn_fail(CTGCN_E_INVALID, what, "null pointer");
     if (!ctgcn_aligned16(pack)) return ctgcn_fail(CTGCN_E_INVALID, what, "pack must be 16-byte aligned");
     GatArgs a{};
     if ((rc = set_gather(a, what, n, d, heads, row_ptr, col, alpha, p_att, key, long_rows, n_long, long_threshold, workspace, workspace_bytes))) return rc;
-    a.src = S; a.ldsrc = lds; a.v = v; a.pack = (const f4 *)pack; a.out1 = R; a.ld1 = ldr; a.sout = csum;
-    if ((rc = dispatch<ROW>(a, float4_rows(a.F, {{S, lds}, {R, ldr}}), stream))) return rc;
+    a.src = S; a.ldsrc = lds; a.v = v; a.pack = (const f4 *)pack; a.out1 = R; a.ld1 = ldr; a.sout = csum; a.lsign = lsign;
+    a.ctr = pyg ? Y : nullptr; a.ldctr = ldy;
+    if ((rc = dispatch<ROW>(a, float4_rows(a.F, {{S, lds}, {R, ldr}, {a.ctr, ldy}}), stream))) return rc;
     PairArgs s{};
-    s.heads = heads; s.F = a.F; s.X = G; s.ldx = ldg; s.Y = R; s.ldy = ldr; s.s1 = csum; s.pack = (f4 *)pack; s.o1 = du;
+    s.heads = heads; s.F = a.F; s.X = G; s.ldx = ldg; s.Y = R; s.ldy = ldr; s.s1 = csum; s.pack = (f4 *)pack; s.o1 = du; s.dsign = -lsign;
     return launch_pairs<DU>(s, n, (hipStream_t)stream);
 }
 
-extern "C" int ctgcn_gat_bwd_col_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *G, int64_t ldg,
-                                     const float *S, int64_t lds, const float *v, const void *pack, const float *a_src, const float *a_dst,
-                                     double alpha, double p_att, uint64_t key, const float *du, float *dS, int64_t ldds, float *B, int64_t ldb,
-                                     float *ksum, float *dv, const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace,
-                                     size_t workspace_bytes, void *stream)
+int bwd_col_impl(const char *what, float lsign, int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *G,
+                 int64_t ldg, const float *S, int64_t lds, const float *v, const void *pack, const float *a_src, const float *a_dst, double alpha,
+                 double p_att, uint64_t key, const float *du, float *dS, int64_t ldds, float *B, int64_t ldb, float *ksum, float *dv,
+                 const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const char *what = "gat_bwd_col";
     int rc = check_shape(what, n, d, heads);
     if (rc < 0) return rc;
     if (bad_scalars(what, alpha, p_att, 0.0, EPI_NONE, rc)) return rc;
@@ -630,12 +694,52 @@ extern "C" int ctgcn_gat_bwd_col_f32(int64_t n, int32_t d, int32_t heads, const 
     if (!ctgcn_aligned16(pack)) return ctgcn_fail(CTGCN_E_INVALID, what, "pack must be 16-byte aligned");
     GatArgs a{};
     if ((rc = set_gather(a, what, n, d, heads, row_ptr, col, alpha, p_att, key, long_rows, n_long, long_threshold, workspace, workspace_bytes))) return rc;
-    a.src = G; a.ldsrc = ldg; a.v = v; a.pack = (const f4 *)pack; a.out1 = dS; a.ld1 = ldds; a.out2 = B; a.ld2 = ldb; a.sout = ksum;
+    a.src = G; a.ldsrc = ldg; a.v = v; a.pack = (const f4 *)pack; a.out1 = dS; a.ld1 = ldds; a.out2 = B; a.ld2 = ldb; a.sout = ksum; a.lsign = lsign;
     if ((rc = dispatch<COL>(a, float4_rows(a.F, {{G, ldg}, {dS, ldds}, {B, ldb}}), stream))) return rc;
     PairArgs s{};
     s.heads = heads; s.F = a.F; s.X = S; s.ldx = lds; s.Y = B; s.ldy = ldb; s.a_src = a_src; s.a_dst = a_dst; s.s1 = ksum; s.s2 = du; s.o1 = dv;
-    s.G = dS; s.ldg = ldds;
+    s.G = dS; s.ldg = ldds; s.dsign = -lsign;
     return launch_pairs<FINISH>(s, n, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int ctgcn_gat_bwd_row_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S, int64_t lds,
+                                     const float *G, int64_t ldg, const float *v, const void *pack, double alpha, double p_att, uint64_t key,
+                                     float *R, int64_t ldr, float *csum, float *du, const int32_t *long_rows, int32_t n_long,
+                                     int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return bwd_row_impl("gat_bwd_row", -1.f, n, d, heads, row_ptr, col, S, lds, G, ldg, nullptr, 0, v, pack, alpha, p_att, key, R, ldr, csum, du, long_rows, n_long,
+                        long_threshold, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ctgcn_tgat_bwd_row_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S, int64_t lds,
+                                      const float *G, int64_t ldg, const float *Y, int64_t ldy, const float *v, const void *pack, double slope,
+                                      float *R, int64_t ldr, float *csum, float *du, const int32_t *long_rows, int32_t n_long,
+                                      int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return bwd_row_impl("tgat_bwd_row", 1.f, n, d, heads, row_ptr, col, S, lds, G, ldg, Y, ldy, v, pack, slope, 0.0, 0, R, ldr, csum, du, long_rows, n_long,
+                        long_threshold, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ctgcn_gat_bwd_col_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *G, int64_t ldg,
+                                     const float *S, int64_t lds, const float *v, const void *pack, const float *a_src, const float *a_dst,
+                                     double alpha, double p_att, uint64_t key, const float *du, float *dS, int64_t ldds, float *B, int64_t ldb,
+                                     float *ksum, float *dv, const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace,
+                                     size_t workspace_bytes, void *stream)
+{
+    return bwd_col_impl("gat_bwd_col", -1.f, n, d, heads, row_ptr, col, G, ldg, S, lds, v, pack, a_src, a_dst, alpha, p_att, key, du, dS, ldds, B, ldb,
+                        ksum, dv, long_rows, n_long, long_threshold, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ctgcn_tgat_bwd_col_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *G, int64_t ldg,
+                                      const float *S, int64_t lds, const float *v, const void *pack, const float *a_tgt, const float *a_src,
+                                      double slope, const float *du, float *dS, int64_t ldds, float *B, int64_t ldb, float *ksum, float *dv,
+                                      const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes,
+                                      void *stream)
+{
+    return bwd_col_impl("tgat_bwd_col", 1.f, n, d, heads, row_ptr, col, G, ldg, S, lds, v, pack, a_tgt, a_src, slope, 0.0, 0, du, dS, ldds, B, ldb, ksum,
+                        dv, long_rows, n_long, long_threshold, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t ctgcn_gat_da_workspace_bytes(int64_t n, int32_t d)

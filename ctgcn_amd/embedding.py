@@ -1,5 +1,6 @@
 """UnsupervisedEmbedding: the reference's unsupervised trainer (reference embedding.py:13-89, 293-368) for CTGCN-C/-S, CGCN-C/-S and the
-EvolveGCN, GCRN, GAT, GIN, SAGE and PGNN baselines (single-output models: trained like the -C models), and for the VGRNN baseline.
+EvolveGCN, GCRN, GAT, GIN, SAGE, PGNN, TgGCN, TgGAT, TgSAGE and TgGIN baselines (single-output models: trained like the -C models), and
+for the VGRNN baseline.
 
 The reference runs, per epoch, one full-graph forward + loss(batch) + backward for each of the ceil(N / batch_size) batches of a
 shuffled node order and steps Adam once after the last batch (gradient accumulation).  The weights do not change inside an epoch
@@ -34,25 +35,30 @@ from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLo
                       VAELoss, _seed_base, epoch_batch_seed)
 
 _S_MODELS = ('CGCN-S', 'CTGCN-S')
-_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT', 'GIN', 'SAGE', 'PGNN', 'VGRNN')      # the baselines: single-output, trained like the -C models
+_TG_MODELS = ('TgGCN', 'TgGAT', 'TgSAGE', 'TgGIN')              # the PyG variants: model(x_list, edge_list) on raw [2, E] indices, no adjacency
+_SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT', 'GIN', 'SAGE', 'PGNN', 'VGRNN') + _TG_MODELS      # the baselines: single-output, trained like the -C models
 
 
 def _check_own_baseline(trainer, model, name):
-    """GIN, SAGE, PGNN and VGRNN are trained as this package's own modules, whose passes run in ctgcn_pool.hip, ctgcn_pgnn.hip and
-    ctgcn_vgrnn.hip.  Another module
+    """GIN, SAGE, PGNN, VGRNN and the four PyG variants are trained as this package's own modules, whose passes run in ctgcn_pool.hip,
+    ctgcn_pgnn.hip, ctgcn_vgrnn.hip and ctgcn_tg.hip.  Another module
     that carries the name (the reference's classes with their dense masks and Python loops, or a model relabelled by hand) has no such
     path and is refused, not run through whatever forward it happens to have."""
-    if name in ('GIN', 'SAGE', 'PGNN', 'VGRNN'):
+    if name in ('GIN', 'SAGE', 'PGNN', 'VGRNN') + _TG_MODELS:
         from . import baseline
         cls = getattr(baseline, name)
         if not isinstance(model, cls):
             raise NotImplementedError("%s trains %s as ctgcn_amd.baseline.%s, got %s" % (trainer, name, name, type(model).__name__))
 
 
-def model_forward(model, x_list, adj_list, node_dist_list, node_num, device):
-    """model(x_list, adj_list), or for a PGNN one draw of anchor sets and model(x_list, dists_max, dists_argmax) (reference
-    embedding.py:209-212); dist_argmax holds node ids when the model carries anchor_node_ids = True"""
-    if getattr(model, 'method_name', None) != 'PGNN':
+def model_forward(model, x_list, adj_list, node_dist_list, node_num, device, edge_list=None):
+    """model(x_list, adj_list); for a PyG variant model(x_list, edge_list) (adj_list may be None); for a PGNN one draw of anchor sets
+    and model(x_list, dists_max, dists_argmax) (reference embedding.py:209-212); dist_argmax holds node ids when the model carries
+    anchor_node_ids = True"""
+    name = getattr(model, 'method_name', None)
+    if name in _TG_MODELS:
+        return model(x_list, edge_list)
+    if name != 'PGNN':
         return model(x_list, adj_list)
     from .baseline.pgnn import preselect_anchor
     dists_max, dists_argmax = preselect_anchor(node_num, node_dist_list, device, node_ids=bool(getattr(model, 'anchor_node_ids', False)))
@@ -62,6 +68,9 @@ def model_forward(model, x_list, adj_list, node_dist_list, node_num, device):
 def _check_edge_list(name, edge_list, steps):
     if name == 'VGRNN' and (edge_list is None or len(edge_list) != steps):
         raise ValueError("a VGRNN needs edge_list: one [2, E] index tensor (or prepared adjacency) per snapshot")
+    if name in _TG_MODELS and (edge_list is None or len(edge_list) != steps):
+        raise ValueError("%s needs edge_list: one [2, E] index tensor (or prepared ops.TgGraph) per snapshot, got %s for %d snapshots"
+                         % (name, "none" if edge_list is None else len(edge_list), steps))
 
 
 def _check_node_dist(name, node_dist_list):
@@ -149,8 +158,8 @@ class UnsupervisedEmbedding(object):
             return emb, struct, struct
         return res, None, res
 
-    def _epoch_fused(self, model, name, x_list, adj_list, node_indices, batch_size, epoch_idx, base, node_dist_list=None):
-        res = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device)
+    def _epoch_fused(self, model, name, x_list, adj_list, node_indices, batch_size, epoch_idx, base, node_dist_list=None, edge_list=None):
+        res = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device, edge_list)
         emb, struct, output_list = self._split(name, res)
         B = batch_count(self.node_num, batch_size)
         if struct is None:
@@ -169,11 +178,11 @@ class UnsupervisedEmbedding(object):
         torch.autograd.backward([o for o, _ in pairs], [g for _, g in pairs])
         return losses.sum(0).tolist(), output_list
 
-    def _epoch_per_batch(self, model, name, x_list, adj_list, node_indices, batch_size, epoch_idx, base, node_dist_list=None):
+    def _epoch_per_batch(self, model, name, x_list, adj_list, node_indices, batch_size, epoch_idx, base, node_dist_list=None, edge_list=None):
         losses, output_list = [], None
         for j, (lo, hi) in enumerate(batch_bounds(self.node_num, batch_size)):
             batch_indices = node_indices[lo:hi]
-            res = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device)
+            res = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device, edge_list)
             emb, struct, output_list = self._split(name, res)
             if struct is None:
                 T = len(emb) if isinstance(emb, list) or emb.dim() == 3 else 1
@@ -199,7 +208,8 @@ class UnsupervisedEmbedding(object):
 
     def learn_embedding(self, adj_list, x_list, edge_list=None, node_dist_list=None, epoch=50, batch_size=1024, lr=1e-3, start_idx=0,
                         weight_decay=0., model_file='ctgcn', load_model=False, shuffle=True, export=True, fused=True):
-        """reference embedding.py:329-368; edge_list is the VGRNN input (required for it, unused otherwise); node_dist_list is what a
+        """reference embedding.py:329-368; edge_list is the input of a VGRNN and of the PyG variants (required for them, unused otherwise;
+        adj_list may then be None for the PyG variants, as the reference's train.py passes it); node_dist_list is what a
         PGNN draws its anchor distances from (required for it, unused otherwise)."""
         model, loss_model, optimizer = self.prepare(load_model, model_file, lr=lr, weight_decay=weight_decay)
         name = self._check_model(model)
@@ -217,7 +227,7 @@ class UnsupervisedEmbedding(object):
             if name == 'VGRNN':
                 self.last_epoch_losses, output_list = self._epoch_vgrnn(model, x_list, adj_list, edge_list, batch_size, fused)
             else:
-                self.last_epoch_losses, output_list = run(model, name, x_list, adj_list, node_indices, batch_size, i, base, node_dist_list)
+                self.last_epoch_losses, output_list = run(model, name, x_list, adj_list, node_indices, batch_size, i, base, node_dist_list, edge_list)
             optimizer.step()            # gradient accumulation over the epoch's batches (embedding.py:349-352)
             model.zero_grad()
             print('epoch', i + 1, ', batches =', len(self.last_epoch_losses), ', loss:', sum(self.last_epoch_losses),
@@ -397,7 +407,7 @@ class SupervisedEmbedding(object):
             embedding_list, _, loss_data_list = model(x_list, edge_list, hx, fused=fused)
             embedding_list = embedding_list[:-1] if learning_type == 'S-link-dy' else embedding_list
             return loss_data_list + [adj_list, classifier(embedding_list, batch_indices)], embedding_list, hx
-        embedding_list = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device)
+        embedding_list = model_forward(model, x_list, adj_list, node_dist_list, self.node_num, self.device, edge_list)
         embedding_list = embedding_list[:-1] if learning_type == 'S-link-dy' else embedding_list
         return classifier(embedding_list, batch_indices), embedding_list, hx
 

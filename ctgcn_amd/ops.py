@@ -2612,6 +2612,285 @@ def batch_norm_act(x, weight, bias, mean=None, var=None, relu=True, p=0.0, key=0
     return _BatchNormAct.apply(_row_view(x), weight.contiguous(), bias.contiguous(), mean, var, bool(relu), p, int(key) & (2 ** 64 - 1), float(eps))
 
 
+# ------------------------------------------------------------------------- PyG variants: TgGCN, TgGAT, TgSAGE, TgGIN (ctgcn_tg.hip)
+TG_EPI_NONE, TG_EPI_RELU = 0, 1
+
+
+class TgGraph(object):
+    """The operators PyG's conv layers read off a raw edge index: edge_index int64 [2, E] on the GPU, row 0 the sources and row 1 the
+    targets (adj._indices() of the loader), n nodes.  Three GcnAdj in pull form (row = target, stored columns = sources, ascending by
+    source), built together on first use by the passes of ctgcn_tg.hip behind one stable sort of the keys target * n + source, and
+    kept:
+        looped   GCNConv's and GATConv's pattern: every non-loop pair (a repeated pair is a repeated entry) and exactly one loop per
+                 node, however many the input had; value dis_s * dis_t, dis_v = c_v^-1/2 over the looped row lengths, formed in fp64
+        mean     the pairs exactly as given (loops and repeats kept, nothing added), value 1 / (entries of the row)
+        sum      the same row_ptr / col, value 1
+    An index outside [0, n), E >= 2^31 - n or n >= 2^31 raises ValueError (one device flag, read once per build)."""
+    builds = 0                              # builds made by this process (the models' cache is checked against it)
+
+    def __init__(self, edge_index, n, long_threshold=None):
+        _need_cuda(edge_index)
+        if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
+            raise ValueError("edge_index must be an int64 [2, E] tensor, got %s %s" % (edge_index.dtype, tuple(edge_index.shape)))
+        self.n, self.E = int(n), int(edge_index.shape[1])
+        if self.n < 0 or self.n >= 2 ** 31:
+            raise ValueError("n = %d outside [0, 2^31)" % self.n)
+        if self.E >= 2 ** 31 - self.n:
+            raise ValueError("E = %d edges with n = %d nodes: E + n must stay below 2^31" % (self.E, self.n))
+        self.edge_index, self.device, self.long_threshold = edge_index, edge_index.device, long_threshold
+        self._adj = None
+
+    def _build(self):
+        lib = _lib.load()
+        E, n, dev = self.E, self.n, self.device
+        src, dst = self.edge_index[0].contiguous(), self.edge_index[1].contiguous()
+        i32 = dict(dtype=torch.int32, device=dev)
+        keys = torch.empty(E, dtype=torch.int64, device=dev)
+        flag = torch.zeros(1, **i32)
+        raw_ptr, loop_at, nloops = torch.empty(n + 1, **i32), torch.empty(n, **i32), torch.empty(n, **i32)
+        col, mean = torch.empty(E, **i32), torch.empty(E, dtype=torch.float32, device=dev)
+        col_l, val_l = torch.empty(E + n, **i32), torch.empty(E + n, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), _timed("tg_csr", n=n, nnz=E):
+            check(lib.ctgcn_tg_keys(E, n, ptr(src), ptr(dst), ptr(keys), ptr(flag), _stream()), "ctgcn_tg_keys")
+            keys = torch.sort(keys, stable=True).values
+            check(lib.ctgcn_tg_csr_count(E, n, ptr(keys), ptr(raw_ptr), ptr(loop_at), ptr(nloops), _stream()), "ctgcn_tg_csr_count")
+            looped_ptr = torch.zeros(n + 1, **i32)
+            looped_ptr[1:] = (raw_ptr[1:] - raw_ptr[:-1] - nloops + 1).cumsum(0)          # E + n < 2^31: no overflow
+            check(lib.ctgcn_tg_csr_emit(E, n, ptr(keys), ptr(raw_ptr), ptr(loop_at), ptr(nloops), ptr(looped_ptr), ptr(col), ptr(mean),
+                                        ptr(col_l), ptr(val_l), _stream()), "ctgcn_tg_csr_emit")
+        bad, nnz_l = torch.cat((flag, looped_ptr[-1:])).tolist()
+        if bad:
+            raise ValueError("edge_index holds a node id outside [0, %d)" % n)
+        TgGraph.builds += 1
+        looped = GcnAdj(looped_ptr, col_l[:nnz_l], val_l[:nnz_l], self.long_threshold)
+        mean_adj = GcnAdj(raw_ptr, col, mean, self.long_threshold)
+        sum_adj = GcnAdj(raw_ptr, col, torch.ones_like(mean), self.long_threshold)
+        self._adj = (looped, mean_adj, sum_adj)
+
+    def _get(self, k):
+        if self._adj is None:
+            self._build()
+        return self._adj[k]
+
+    looped = property(lambda self: self._get(0))
+    mean = property(lambda self: self._get(1))
+    sum = property(lambda self: self._get(2))
+
+
+def _tg_conv_fwd(adj, S, T, self_scale, bias, epi, p=0.0, key=0):
+    """Y: ctgcn_tg_conv_fwd_f32"""
+    lib = _lib.load()
+    n, d = S.shape
+    Y = torch.empty(n, d, dtype=torch.float32, device=S.device)
+    with torch.cuda.device(S.device), _timed("tg_conv_fwd", n=n, d=d, nnz=adj.nnz):
+        check(lib.ctgcn_tg_conv_fwd_f32(n, d, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(S), S.stride(0), ptr(T), 0 if T is None else T.stride(0),
+                                        float(self_scale), ptr(bias), ptr(Y), Y.stride(0), epi, p, key, *_gcn_long(adj, d), _stream()),
+              "ctgcn_tg_conv_fwd_f32")
+    return Y
+
+
+def _tg_conv_prep(dY, Y, bias, epi, p=0.0, key=0, want_db=False, out=None):
+    """(G, db): ctgcn_tg_conv_prep_f32.  G is dY itself for TG_EPI_NONE, else written to out when given; db None unless wanted."""
+    n, d = dY.shape
+    dev = dY.device
+    if epi == TG_EPI_NONE and not want_db:
+        return dY, None
+    lib = _lib.load()
+    G = (torch.empty(n, d, dtype=torch.float32, device=dev) if out is None else out) if epi != TG_EPI_NONE else None
+    db = torch.zeros(d, dtype=torch.float32, device=dev) if want_db else None
+    nbytes = int(lib.ctgcn_tg_prep_workspace_bytes(n, d)) if want_db else 0
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if want_db else None
+    with torch.cuda.device(dev), _timed("tg_conv_prep", n=n, d=d):
+        check(lib.ctgcn_tg_conv_prep_f32(n, d, ptr(dY), dY.stride(0), ptr(Y), 0 if Y is None else Y.stride(0), ptr(bias), epi, p, key, ptr(G),
+                                         0 if G is None else G.stride(0), ptr(db), ptr(ws), nbytes, _stream()), "ctgcn_tg_conv_prep_f32")
+    return (dY if G is None else G), db
+
+
+class _TgConv(torch.autograd.Function):
+    """S, T: [n, d], T or None.  pair: S is Z [n, 2 d] = [S | T], whose gradient is written as one buffer.  same: T is S."""
+
+    @staticmethod
+    def forward(ctx, S, T, bias, adj, scale, epi, p, key, pair, same):
+        if pair:
+            d = S.shape[1] // 2
+            Y = _tg_conv_fwd(adj, S[:, :d], S[:, d:], scale, bias, epi, p, key)
+        else:
+            Y = _tg_conv_fwd(adj, S, S if same else T, scale, bias, epi, p, key)
+        ctx.adj, ctx.cfg = adj, (scale, epi, p, key, pair, same)
+        ctx.save_for_backward(*((Y,) if epi != TG_EPI_NONE else ()))
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        scale, epi, p, key, pair, same = ctx.cfg
+        need_S, need_T, need_b = ctx.needs_input_grad[:3]
+        dY = _row_view(dY)
+        n, d = dY.shape
+        Y = ctx.saved_tensors[0] if epi != TG_EPI_NONE else None
+        if pair and not need_S:                                         # the bias gradient alone
+            return None, None, _tg_conv_prep(dY, Y, None, epi, p, key, want_db=need_b)[1], None, None, None, None, None, None, None
+        adj_t = ctx.adj.transposed()
+        if pair:
+            dZ = torch.empty(n, 2 * d, dtype=torch.float32, device=dY.device)
+            direct = scale == 1.0 and epi != TG_EPI_NONE                # dT = G: the pre-pass writes it in place
+            G, db = _tg_conv_prep(dY, Y, None, epi, p, key, want_db=need_b, out=dZ[:, d:] if direct else None)
+            if not direct:
+                torch.mul(G, scale, out=dZ[:, d:])
+            _gcn_conv_fwd(adj_t, G, None, GCN_EPI_NONE, out=dZ[:, :d])
+            return dZ, None, db, None, None, None, None, None, None, None
+        G, db = _tg_conv_prep(dY, Y, None, epi, p, key, want_db=need_b)
+        dS = dT = None
+        if same:
+            if need_S:                                                 # dS = Â^T G + self_scale G, the forward's own pass over Â^T
+                dS = _tg_conv_fwd(adj_t, G, G, scale, None, TG_EPI_NONE)
+        else:
+            if need_S:
+                dS = _gcn_conv_fwd(adj_t, G, None, GCN_EPI_NONE)[0]
+            if need_T:
+                dT = G if scale == 1.0 else G * scale
+        return dS, dT, db, None, None, None, None, None, None, None
+
+
+def tg_conv(S, adj, T=None, self_scale=1.0, bias=None, epi=TG_EPI_NONE, p=0.0, key=0):
+    """Y = epi(Â S + self_scale T + bias) for any GcnAdj, differentiable in S, T and bias.  T [n, d] may be None, S itself, or the
+    other half of one contiguous [n, 2 d] buffer [S | T].  epi: TG_EPI_NONE, or TG_EPI_RELU: ReLU, then dropout with probability p
+    when p > 0 (entry (i, c) kept iff u01(key, i, c) >= p, kept entries scaled by 1 / (1 - p): gcn_conv's draw).  One pass is PyG's
+    SAGEConv after its product of width 2 d (adj = TgGraph.mean, bias = lin_l's) or its GINConv after the Linear, which commutes with
+    the sum (adj = TgGraph.sum, T = S, self_scale = 1 + eps).  The backward is one N x d pre-pass (the gradient before the epilogue,
+    the mask made again from key, and the bias gradient in a fixed block order), dT = self_scale G and the plain aggregation
+    dS = Â^T G over adj.transposed().  No float atomics and no stored mask: repeated calls are bit-identical."""
+    _need_cuda(S, T, bias, adj.val)
+    if epi not in (TG_EPI_NONE, TG_EPI_RELU):
+        raise ValueError("epi must be TG_EPI_NONE or TG_EPI_RELU")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p must lie in [0, 1), got %r" % p)
+    if S.dim() != 2 or S.shape[0] != adj.n:
+        raise ValueError("S must be [%d, d], got %s" % (adj.n, tuple(S.shape)))
+    if T is not None and tuple(T.shape) != tuple(S.shape):
+        raise ValueError("T must be %s, got %s" % (tuple(S.shape), tuple(T.shape)))
+    if any(t is not None and t.dtype != torch.float32 for t in (S, T, bias)):
+        raise TypeError("fp32 features and bias expected")
+    if any(t is not None and t.device != adj.device for t in (S, T, bias)):
+        raise ValueError("S, T, bias and the adjacency must be on one device")
+    if bias is not None and tuple(bias.shape) != (S.shape[1],):
+        raise ValueError("bias must have %d entries" % S.shape[1])
+    n, d = S.shape
+    scale, key = float(self_scale), int(key) & (2 ** 64 - 1)
+    bias = None if bias is None else bias.contiguous()
+    if T is S:
+        return _TgConv.apply(_row_view(S), None, bias, adj, scale, int(epi), p, key, False, True)
+    # the two halves of one [n, 2 d] buffer as [S | T]: the gradient is assembled in one buffer, with no zero-padded halves to add
+    if (T is not None and S._base is not None and S._base is T._base and S._base.dim() == 2 and S._base.is_contiguous()
+            and tuple(S._base.shape) == (n, 2 * d) and S.storage_offset() == S._base.storage_offset()
+            and T.storage_offset() == S.storage_offset() + d and S.stride() == T.stride() == S._base.stride()):
+        return _TgConv.apply(S._base, None, bias, adj, scale, int(epi), p, key, True, False)
+    return _TgConv.apply(_row_view(S), None if T is None else _row_view(T), bias, adj, scale, int(epi), p, key, False, False)
+
+
+def _tgat_fwd(adj, S, a_tgt, a_src, heads, slope, bias, epi, p=0.0, key=0):
+    """(out, Y, u, v, m, Z): ctgcn_tgat_fwd_f32.  Y is the sum before the bias and the epilogue: out itself without either."""
+    lib = _lib.load()
+    n, d = S.shape
+    dev = S.device
+    out = torch.empty(n, d, dtype=torch.float32, device=dev)
+    Y = torch.empty(n, d, dtype=torch.float32, device=dev) if (epi != TG_EPI_NONE or bias is not None) else None
+    u, v, m, Z = (torch.empty(n, heads, dtype=torch.float32, device=dev) for _ in range(4))
+    with torch.cuda.device(dev), _timed("tgat_fwd", n=n, d=d, heads=heads, nnz=adj.nnz):
+        check(lib.ctgcn_tgat_fwd_f32(n, d, heads, ptr(adj.row_ptr), ptr(adj.col), ptr(S), S.stride(0), ptr(a_tgt), ptr(a_src), slope, ptr(bias), epi,
+                                     p, key, ptr(out), out.stride(0), ptr(Y), 0 if Y is None else Y.stride(0), ptr(u), ptr(v), ptr(m), ptr(Z),
+                                     *_gat_long(adj, d, heads), _stream()), "ctgcn_tgat_fwd_f32")
+    return out, (out if Y is None else Y), u, v, m, Z
+
+
+def _tgat_bwd_row(adj, S, G, Y, v, pack, heads, slope):
+    """du [n, heads]: ctgcn_tgat_bwd_row_f32 over the CSR; Y the forward's sums before the bias"""
+    lib = _lib.load()
+    n, d = S.shape
+    dev = S.device
+    R = torch.empty(n, d, dtype=torch.float32, device=dev)
+    csum, du = (torch.empty(n, heads, dtype=torch.float32, device=dev) for _ in range(2))
+    with torch.cuda.device(dev), _timed("tgat_bwd_row", n=n, d=d, heads=heads, nnz=adj.nnz):
+        check(lib.ctgcn_tgat_bwd_row_f32(n, d, heads, ptr(adj.row_ptr), ptr(adj.col), ptr(S), S.stride(0), ptr(G), G.stride(0), ptr(Y), Y.stride(0), ptr(v),
+                                         ptr(pack), slope, ptr(R), R.stride(0), ptr(csum), ptr(du), *_gat_long(adj, d, heads), _stream()),
+              "ctgcn_tgat_bwd_row_f32")
+    return du
+
+
+def _tgat_bwd_col(adj_t, S, G, v, pack, a_tgt, a_src, heads, slope, du=None):
+    """(dS or None, dv [n, heads]): ctgcn_tgat_bwd_col_f32 over the transposed CSR; dS only with du"""
+    lib = _lib.load()
+    n, d = S.shape
+    dev = S.device
+    dS = torch.empty(n, d, dtype=torch.float32, device=dev) if du is not None else None
+    B = torch.empty(n, d, dtype=torch.float32, device=dev)
+    ksum, dv = (torch.empty(n, heads, dtype=torch.float32, device=dev) for _ in range(2))
+    with torch.cuda.device(dev), _timed("tgat_bwd_col", n=n, d=d, heads=heads, nnz=adj_t.nnz):
+        check(lib.ctgcn_tgat_bwd_col_f32(n, d, heads, ptr(adj_t.row_ptr), ptr(adj_t.col), ptr(G), G.stride(0), ptr(S), S.stride(0), ptr(v), ptr(pack),
+                                         ptr(a_tgt), ptr(a_src), slope, ptr(du), ptr(dS), 0 if dS is None else dS.stride(0), ptr(B), B.stride(0),
+                                         ptr(ksum), ptr(dv), *_gat_long(adj_t, d, heads), _stream()), "ctgcn_tgat_bwd_col_f32")
+    return dS, dv
+
+
+class _TgatConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S, a_tgt, a_src, bias, adj, heads, slope, epi, p, key):
+        out, Y, u, v, m, Z = _tgat_fwd(adj, S, a_tgt, a_src, heads, slope, bias, epi, p, key)
+        ctx.adj, ctx.cfg = adj, (heads, slope, epi, p, key)
+        ctx.save_for_backward(S, a_tgt, a_src, bias, Y, u, v, m, Z)
+        return out
+
+    @staticmethod
+    def backward(ctx, dY):
+        S, a_tgt, a_src, bias, Y, u, v, m, Z = ctx.saved_tensors
+        heads, slope, epi, p, key = ctx.cfg
+        need_dS, need_tgt, need_src, need_b = ctx.needs_input_grad[:4]
+        dS = da_tgt = da_src = db = None
+        G, db = _tg_conv_prep(_row_view(dY), Y, bias, epi, p, key, want_db=need_b)
+        if need_dS or need_tgt or need_src:
+            _, pack = _gat_bwd_prep(G, Y, u, m, Z, heads, GAT_EPI_NONE)
+            du = _tgat_bwd_row(ctx.adj, S, G, Y, v, pack, heads, slope) if (need_dS or need_tgt) else None
+            if need_dS or need_src:
+                dS, dv = _tgat_bwd_col(ctx.adj.transposed(), S, G, v, pack, a_tgt, a_src, heads, slope, du if need_dS else None)
+            if need_tgt or need_src:
+                da_tgt, da_src = _gat_da(S, du if need_tgt else None, dv if need_src else None, heads)
+        return (dS, da_tgt, da_src, db) + (None,) * 6
+
+
+def tgat_conv(S, a_tgt, a_src, adj, heads=1, slope=0.2, bias=None, epi=TG_EPI_NONE, p=0.0, key=0):
+    """PyG's GATConv after its product, over the pattern of any GcnAdj (TgGraph.looped for the layer itself; the values are not read),
+    differentiable in S, a_tgt, a_src and bias.  S [n, heads F]; a_tgt / a_src [heads, F] are PyG's att_r (the target's, the row's
+    own features) and att_l (the source's, the gathered ones).  For a stored entry (i, j) and head h:
+        z = a_tgt_h · S_i^h + a_src_h · S_j^h,  l = leakyrelu_slope(z),  e = exp(l - max_j l),  Y_i^h = (sum_j e S_j^h) / sum_j e
+    and the result is epi(Y + bias), epi as in tg_conv.  There is no attention dropout (GATConv's own defaults to 0).  An empty row
+    gives epi(bias) and no gradient to S.  The passes are ops.gat_conv's with the logit's sign turned (ctgcn_gat.hip); the backward
+    computes only the gradients that are asked for, and nothing of nnz x F elements is stored."""
+    _need_cuda(S, a_tgt, a_src, bias, adj.val)
+    heads = int(heads)
+    if epi not in (TG_EPI_NONE, TG_EPI_RELU):
+        raise ValueError("epi must be TG_EPI_NONE or TG_EPI_RELU")
+    p, slope = float(p), float(slope)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p must lie in [0, 1), got %r" % p)
+    if slope != slope or slope in (float("inf"), float("-inf")):
+        raise ValueError("slope must be finite")
+    if S.dim() != 2 or S.shape[0] != adj.n:
+        raise ValueError("S must be [%d, d], got %s" % (adj.n, tuple(S.shape)))
+    if heads < 1 or S.shape[1] < 1 or S.shape[1] % heads:
+        raise ValueError("d = %d is not a positive multiple of heads = %d" % (S.shape[1], heads))
+    want = (heads, S.shape[1] // heads)
+    if tuple(a_tgt.shape) != want or tuple(a_src.shape) != want:
+        raise ValueError("a_tgt and a_src must be [%d, %d]" % want)
+    if bias is not None and tuple(bias.shape) != (S.shape[1],):
+        raise ValueError("bias must have %d entries" % S.shape[1])
+    if any(t is not None and t.dtype != torch.float32 for t in (S, a_tgt, a_src, bias)):
+        raise TypeError("fp32 features, attention vectors and bias expected")
+    if any(t is not None and t.device != adj.device for t in (S, a_tgt, a_src, bias)):
+        raise ValueError("S, a_tgt, a_src, bias and the adjacency must be on one device")
+    return _TgatConv.apply(_row_view(S), a_tgt.contiguous(), a_src.contiguous(), None if bias is None else bias.contiguous(), adj, heads, slope,
+                           int(epi), p, int(key) & (2 ** 64 - 1))
+
+
 # ------------------------------------------------------------------------- P-GNN baseline (ctgcn_pgnn.hip)
 PGNN_EPI_NONE, PGNN_EPI_NORM = 0, 1
 PGNN_PULL_PIECE = 512            # (n, a) items per piece of a pull list of the backward (one wave per piece)

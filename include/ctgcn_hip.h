@@ -962,6 +962,64 @@ int ctgcn_gat_bwd_col_f32(int64_t n, int32_t d, int32_t heads, const int32_t *ro
                           void *stream);
 
 /*
+ * PyTorch-Geometric variants of the GCN, GAT, GraphSAGE and GIN baselines (reference TgGCN, TgGAT, TgSAGE, TgGIN;
+ * ctgcn_amd/baseline/tg.py), ctgcn_tg.hip and the PyG-form entry points of ctgcn_gat.hip.
+ *
+ * The operator of a raw edge index (src / dst int64 [E], node ids in [0, n); row = target, stored columns = sources):
+ * ctgcn_tg_keys: keys[e] = dst[e] · n + src[e]; an index outside [0, n) gives the key n · n and sets *flag (int32, zeroed by the caller).
+ * ctgcn_tg_csr_count: over the keys sorted ascending.  raw_ptr [n + 1]: row pointers of the pairs as given; loop_at [n]: the entries
+ *   of row v whose source is below v; nloops [n]: the loops (v, v) the input holds.  Binary searches, no atomics.
+ * ctgcn_tg_csr_emit: col [E] = the sources in key order, mean [E] = 1 / (entries of the row).  The looped pattern of GCNConv and
+ *   GATConv over looped_ptr [n + 1] (row length c_v = raw length − nloops[v] + 1, scanned by the caller): every non-loop entry at its
+ *   sorted position, a repeated pair as a repeated entry, exactly one loop per node; val_l = dis_s · dis_t with dis_v = c_v^-1/2,
+ *   formed in fp64 and rounded once.  col_l / val_l hold looped_ptr[n] <= E + n entries.
+ * Need 0 <= n < 2^31 and 0 <= E < 2^31 − n (CTGCN_E_INVALID otherwise).
+ *
+ * ctgcn_tg_conv_fwd_f32: Y[i] = epi(Σ_e val[e] · S[col[e]] + self_scale · T[i] + bias) over a CSR with the long-row rules of
+ *   ctgcn_gcn_conv_fwd_f32.  T and bias may be null; T may be S or another column slice of S's buffer.  epi 0 none; 1 ReLU, then
+ *   dropout when p > 0: entry (i, c) kept iff u01(key, i, c) >= p and scaled by 1 / (1 − p).
+ * ctgcn_tg_conv_prep_f32: the backward's N x d pass.  With epi 1, G = dY where Y + bias > 0 (bias null: Y alone, the saved output)
+ *   and the draw, made again from key, kept the entry (scaled by 1 / (1 − p)), else 0; with epi 0 nothing is written and G = dY.
+ *   db [d], when not null, receives Σ_i G[i]: per-block partial sums in the workspace (ctgcn_tg_prep_workspace_bytes(n, d) bytes,
+ *   16-byte aligned), added in block order by a second launch.  epi 0 without db is refused: there is nothing to compute.
+ *
+ * ctgcn_tgat_fwd_f32, ctgcn_tgat_bwd_row_f32, ctgcn_tgat_bwd_col_f32: ctgcn_gat_*'s passes in GATConv's form.  a_tgt pairs with the
+ *   row's own features (u_i = a_tgt_h · S_i^h), a_src with the gathered ones (v_j = a_src_h · S_j^h); l = +leakyrelu_slope(u_i + v_j),
+ *   m_i = max_j l, Y_i^h = (Σ_j e S_j^h) / Z_i, out = epi(Y + bias) with epi and the dropout of ctgcn_tg_conv_fwd_f32; no attention
+ *   dropout.  Y [n, d] receives the sums before the bias whenever bias is not null or epi is 1 (else out is Y and Y may be null); an
+ *   empty row gives Y = 0, out = epi(bias).  The backward takes G from ctgcn_tg_conv_prep_f32 (Y, bias) and pack from
+ *   ctgcn_gat_bwd_prep_f32 with epi 0 on that G; du_i = G_i^h · R_i^h − D_i csum_i and dv_j = S_j^h · B_j^h − ksum_j (dl / dz = s
+ *   where the reference form has −s); ctgcn_gat_da_f32 is shared.  The row pass sums with s − s0_i in place of s, s0_i the slope at
+ *   the row's largest logit: Σ_j p (t − D_i) = 0, so du is unchanged, and exactly 0 for a row whose logits share a sign.  It also
+ *   takes Y (the forward's sums before the bias) and gathers S_j − Y_i: t − D_i = G_i · (S_j − Y_i), so du_i = G_i^h · R_i^h with csum
+ *   left at 0, and a component all S_j share never enters the sum.
+ * Argument checks, long rows, float4 rule and determinism as for the entry points they stand beside.
+ */
+int ctgcn_tg_keys(int64_t E, int64_t n, const int64_t *src, const int64_t *dst, int64_t *keys, int32_t *flag, void *stream);
+int ctgcn_tg_csr_count(int64_t E, int64_t n, const int64_t *keys, int32_t *raw_ptr, int32_t *loop_at, int32_t *nloops, void *stream);
+int ctgcn_tg_csr_emit(int64_t E, int64_t n, const int64_t *keys, const int32_t *raw_ptr, const int32_t *loop_at, const int32_t *nloops,
+                      const int32_t *looped_ptr, int32_t *col, float *mean, int32_t *col_l, float *val_l, void *stream);
+int ctgcn_tg_conv_fwd_f32(int64_t n, int32_t d, const int32_t *row_ptr, const int32_t *col, const float *val, const float *S, int64_t lds,
+                          const float *T, int64_t ldt, float self_scale, const float *bias, float *Y, int64_t ldy, int32_t epi, double p,
+                          uint64_t key, const int32_t *long_rows, int32_t n_long, int32_t long_threshold, void *workspace,
+                          size_t workspace_bytes, void *stream);
+size_t ctgcn_tg_prep_workspace_bytes(int64_t n, int32_t d);
+int ctgcn_tg_conv_prep_f32(int64_t n, int32_t d, const float *dY, int64_t lddy, const float *Y, int64_t ldy, const float *bias, int32_t epi,
+                           double p, uint64_t key, float *G, int64_t ldg, float *db, void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_tgat_fwd_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S, int64_t lds,
+                       const float *a_tgt, const float *a_src, double slope, const float *bias, int32_t epi, double p, uint64_t key,
+                       float *out, int64_t ldout, float *Y, int64_t ldy, float *u, float *v, float *m, float *Z, const int32_t *long_rows,
+                       int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_tgat_bwd_row_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *S, int64_t lds,
+                           const float *G, int64_t ldg, const float *Y, int64_t ldy, const float *v, const void *pack, double slope, float *R,
+                           int64_t ldr, float *csum, float *du, const int32_t *long_rows, int32_t n_long, int32_t long_threshold,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int ctgcn_tgat_bwd_col_f32(int64_t n, int32_t d, int32_t heads, const int32_t *row_ptr, const int32_t *col, const float *G, int64_t ldg,
+                           const float *S, int64_t lds, const float *v, const void *pack, const float *a_tgt, const float *a_src, double slope,
+                           const float *du, float *dS, int64_t ldds, float *B, int64_t ldb, float *ksum, float *dv, const int32_t *long_rows,
+                           int32_t n_long, int32_t long_threshold, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Pooling layers of the GIN and GraphSAGE baselines (reference baseline/gin.py, baseline/sage.py; ctgcn_amd/baseline/gin.py, sage.py),
  * ctgcn_pool.hip.  Same CSR and long-row rules as ctgcn_gcn_conv_fwd_f32; the matrix need not be symmetric.
  *
