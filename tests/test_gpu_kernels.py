@@ -89,8 +89,9 @@ def test_kcore_level_cap_reports_min_of_core_and_cap():
 
 
 def test_kcore_long_path_and_queue_spill():
-    """a 300k-vertex path (every vertex peels at level 1 through a chain of pushes) and a graph whose
-    level-k frontier exceeds one block's LDS queue."""
+    """a 300k-vertex path and a forest of 40 stars with 20 000 leaves each, uncapped: ctgcn_kcore_i32 routes an uncapped call to the
+    h-index sweeps, so this is their long tail (one sweep per two hops of the path, batch after batch) and their hub kernel, not the
+    peel.  The LDS queue spill of kcore_level_kernel that the name speaks of is tested in tests/test_gpu_kcore_shapes.py (peel queue)."""
     from ctgcn_amd import ops
     from oracle import oracle as O
     n = 300000
