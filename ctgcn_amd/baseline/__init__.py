@@ -1,5 +1,5 @@
 """Methods CTGCN is compared against (the reference's `baseline` package), on the same HIP library."""
-from .dynae import BatchGenerator, BatchPredictor, DynAE, DynamicEmbedding, DynGraph2VecLoss, RegularizationLoss  # noqa: F401  (its MLP: baseline.dynae.MLP)
+from .dynae import BatchGenerator, BatchPredictor, DynAE, DynamicEmbedding, DynGraph2VecLoss, RegularizationLoss, dyngem_embedding  # noqa: F401  (its MLP: baseline.dynae.MLP)
 from .dyngem import DynGEM, DynGEMBatchGenerator, DynGEMBatchPredictor, DynGEMLoss  # noqa: F401
 from .dynrnn import MLLSTM, DynRNN  # noqa: F401
 from .dynaernn import MTMLP, DynAERNN  # noqa: F401

@@ -26,7 +26,7 @@ Reference behaviour that is reproduced because results depend on it:
     both sums by the number of weights, and returns a zero of shape [1] when both nu are 0.
   * Prediction reads the last look_back snapshots, as adj_list[train_size:] does.  The predictors run the encoder only unless the
     reconstruction is asked for (need_pred=True, the default, returns (embedding, x_pred) as the reference does).
-Not ported: the dyngem_embedding(method, args) driver, like every other driver."""
+dyngem_embedding(method, args) is the reference's driver of the four methods over these classes."""
 import os
 import time
 
@@ -419,3 +419,96 @@ class DynamicEmbedding(object):
         del embedding_mat
         torch.cuda.empty_cache()
         return cost_time
+
+
+def dyngem_embedding(method, args):
+    """The reference's driver of DynGEM, DynAE, DynRNN and DynAERNN (baseline/dynAE.py:331-425) from a method's config section: one
+    window per idx in the configured range, covering the snapshots idx - duration + 1 .. idx, with a fresh model, loss, generator and
+    predictor each; with load_model a window starts from the checkpoint the previous one wrote (DynGEM's warm start).  The window's
+    scipy matrices go to DynamicEmbedding.learn_embedding as the loader returns them.  The optional `seed` key (not the reference's)
+    seeds torch, numpy.random and random before each window."""
+    assert method in ['DynGEM', 'DynAE', 'DynRNN', 'DynAERNN']
+    import pandas as pd
+    from ..helper import DataLoader
+    from ..train import resolve_range, seed_everything, write_time_file
+    from .dynaernn import DynAERNN
+    from .dyngem import DynGEM, DynGEMBatchGenerator, DynGEMBatchPredictor, DynGEMLoss
+    from .dynrnn import DynRNN
+    model_dict = {'DynGEM': DynGEM, 'DynAE': DynAE, 'DynRNN': DynRNN, 'DynAERNN': DynAERNN}
+
+    base_path = args['base_path']
+    origin_folder = args['origin_folder']
+    embedding_folder = args['embed_folder']
+    model_folder = args['model_folder']
+    model_file = args['model_file']
+    file_sep = args['file_sep']
+    duration = args['duration']
+    embed_dim = args['embed_dim']
+    has_cuda = args['has_cuda']
+    epoch = args['epoch']
+    lr = args['lr']
+    batch_size = args['batch_size']
+    load_model = args['load_model']
+    shuffle = args['shuffle']
+    export = args['export']
+    record_time = args['record_time']
+    seed = args.get('seed', None)
+
+    n_units, ae_units, rnn_units = [], [], []
+    look_back, alpha = 0, 0
+    if method in ['DynGEM', 'DynAE', 'DynRNN']:
+        n_units = args['n_units']
+    else:
+        ae_units = args['ae_units']
+        rnn_units = args['rnn_units']
+    if method in ['DynAE', 'DynRNN', 'DynAERNN']:
+        look_back = args['look_back']
+        assert look_back > 0
+    else:
+        alpha = args['alpha']
+    beta = args['beta']
+    nu1 = args['nu1']
+    nu2 = args['nu2']
+    bias = args['bias']
+
+    origin_base_path = os.path.abspath(os.path.join(base_path, origin_folder))
+    max_time_num = len(os.listdir(origin_base_path))
+    node_list = pd.read_csv(os.path.abspath(os.path.join(base_path, args['node_file'])), names=['node'])['node'].tolist()
+    node_num = len(node_list)
+    data_loader = DataLoader(node_list, max_time_num, has_cuda=has_cuda)
+    start_idx, end_idx = resolve_range(max_time_num, args['start_idx'], args['end_idx'])
+
+    if method == 'DynGEM':
+        assert duration == 1
+    assert start_idx + 1 - duration >= 0
+    assert duration > look_back
+
+    t1 = time.time()
+    time_list = []
+    print('start ' + method + ' embedding!')
+    for idx in range(start_idx, end_idx):
+        print('idx = ', idx)
+        seed_everything(seed)
+        # the raw adjacency matrices are the input: no normalisation, no self loops
+        adj_list = data_loader.get_date_adj_list(origin_base_path, start_idx=idx - duration + 1, duration=duration, sep=file_sep,
+                                                 normalize=False, add_eye=False, data_type='matrix')
+        model = model_dict[method](input_dim=node_num, output_dim=embed_dim, look_back=look_back, n_units=n_units, ae_units=ae_units,
+                                   rnn_units=rnn_units, bias=bias)
+        if method == 'DynGEM':
+            loss = DynGEMLoss(alpha=alpha, beta=beta, nu1=nu1, nu2=nu2)
+            batch_generator = DynGEMBatchGenerator(node_list=node_list, batch_size=batch_size, beta=beta, shuffle=shuffle, has_cuda=has_cuda)
+            batch_predictor = DynGEMBatchPredictor(node_list=node_list, batch_size=batch_size, has_cuda=has_cuda)
+        else:
+            loss = DynGraph2VecLoss(beta=beta, nu1=nu1, nu2=nu2)
+            batch_generator = BatchGenerator(node_list=node_list, batch_size=batch_size, look_back=look_back, beta=beta, shuffle=shuffle,
+                                             has_cuda=has_cuda)
+            batch_predictor = BatchPredictor(node_list=node_list, batch_size=batch_size, has_cuda=has_cuda)
+        trainer = DynamicEmbedding(base_path=base_path, origin_folder=origin_folder, embedding_folder=embedding_folder, node_list=node_list,
+                                   model=model, loss=loss, batch_generator=batch_generator, batch_predictor=batch_predictor,
+                                   model_folder=model_folder, has_cuda=has_cuda)
+        time_list.append(trainer.learn_embedding(adj_list, epoch=epoch, lr=lr, idx=idx, model_file=model_file, load_model=load_model,
+                                                 export=export))
+
+    if record_time:
+        write_time_file(base_path, method, time_list)
+    print('finish ' + method + ' embedding! cost time: ', time.time() - t1, ' seconds!')

@@ -1,5 +1,5 @@
 """UnsupervisedEmbedding: the reference's unsupervised trainer (reference embedding.py:13-89, 293-368) for CTGCN-C/-S, CGCN-C/-S and the
-EvolveGCN, GCRN, GAT, GIN, SAGE, PGNN, TgGCN, TgGAT, TgSAGE and TgGIN baselines (single-output models: trained like the -C models), and
+EvolveGCN, GCRN, GCN, GAT, GIN, SAGE, PGNN, TgGCN, TgGAT, TgSAGE and TgGIN baselines (single-output models: trained like the -C models), and
 for the VGRNN baseline.
 
 The reference runs, per epoch, one full-graph forward + loss(batch) + backward for each of the ceil(N / batch_size) batches of a
@@ -37,6 +37,22 @@ from .metrics import (ClassificationLoss, NegativeSamplingLoss, ReconstructionLo
 _S_MODELS = ('CGCN-S', 'CTGCN-S')
 _TG_MODELS = ('TgGCN', 'TgGAT', 'TgSAGE', 'TgGIN')              # the PyG variants: model(x_list, edge_list) on raw [2, E] indices, no adjacency
 _SUPPORTED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S', 'EvolveGCN', 'GCRN', 'GAT', 'GIN', 'SAGE', 'PGNN', 'VGRNN') + _TG_MODELS      # the baselines: single-output, trained like the -C models
+# trained too, but only as this package's own class (the driver sends GCN through the trainers like every other method); not in _SUPPORTED:
+# another module that carries the name is still refused as an unsupported method
+_MODULE_TRAINED = ('GCN',)
+
+
+def _supported_name(trainer, model):
+    """the model's method_name when the trainer covers it, NotImplementedError otherwise"""
+    name = getattr(model, 'method_name', None)
+    if name in _MODULE_TRAINED:
+        from . import baseline
+        if isinstance(model, getattr(baseline, name)):
+            return name
+    elif name in _SUPPORTED:
+        return name
+    raise NotImplementedError("%s covers %s, and %s as ctgcn_amd.baseline's own module, not %r (%s)"
+                              % (trainer, ', '.join(_SUPPORTED), ', '.join(_MODULE_TRAINED), name, type(model).__name__))
 
 
 def _check_own_baseline(trainer, model, name):
@@ -136,9 +152,7 @@ class UnsupervisedEmbedding(object):
         return batch_count(self.node_num, batch_size)
 
     def _check_model(self, model):
-        name = getattr(model, 'method_name', None)
-        if name not in _SUPPORTED:
-            raise NotImplementedError("UnsupervisedEmbedding covers %s, not %r" % (', '.join(_SUPPORTED), name))
+        name = _supported_name("UnsupervisedEmbedding", model)
         _check_own_baseline("UnsupervisedEmbedding", model, name)
         want = VAELoss if name == 'VGRNN' else ReconstructionLoss if name in _S_MODELS else NegativeSamplingLoss
         if not isinstance(self.loss, want):
@@ -412,9 +426,7 @@ class SupervisedEmbedding(object):
         return classifier(embedding_list, batch_indices), embedding_list, hx
 
     def _check_model(self, model):
-        name = getattr(model, 'method_name', None)
-        if name not in _SUPPORTED:
-            raise NotImplementedError("SupervisedEmbedding covers %s, not %r" % (', '.join(_SUPPORTED), name))
+        name = _supported_name("SupervisedEmbedding", model)
         _check_own_baseline("SupervisedEmbedding", model, name)
         want = VAEClassificationLoss if name == 'VGRNN' else StructureClassificationLoss if name in _S_MODELS else ClassificationLoss
         if not isinstance(self.loss, want):

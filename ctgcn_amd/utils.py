@@ -17,6 +17,34 @@ def get_format_str(cnt):
     return '{:0>' + str(len(str(int(cnt))) if cnt > 0 else 0) + 'd}'
 
 
+# Method tables of the driver (reference utils.py:159-182): the reference's names in the reference's order.  The reference returns
+# dicts of ones built with np.int; tuples serve the same `in` tests and keep the order.
+_STATIC_GNN = ('GCN', 'TgGCN', 'GAT', 'TgGAT', 'SAGE', 'TgSAGE', 'GIN', 'TgGIN', 'PGNN', 'CGCN-C', 'CGCN-S')
+_DYNAMIC_GNN = ('GCRN', 'EvolveGCN', 'VGRNN', 'CTGCN-C', 'CTGCN-S')
+_CORE_BASED = ('CGCN-C', 'CGCN-S', 'CTGCN-C', 'CTGCN-S')
+_NON_GNN = ('DynGEM', 'DynAE', 'DynRNN', 'DynAERNN', 'TIMERS')
+
+
+def get_static_gnn_methods():
+    return _STATIC_GNN
+
+
+def get_dynamic_gnn_methods():
+    return _DYNAMIC_GNN
+
+
+def get_core_based_methods():
+    return _CORE_BASED
+
+
+def get_supported_gnn_methods():
+    return _STATIC_GNN + _DYNAMIC_GNN
+
+
+def get_supported_methods():
+    return _NON_GNN + _STATIC_GNN + _DYNAMIC_GNN
+
+
 class NodeIndex(object):
     """Node name -> row index join for whole columns at once (Arrow hash join), built once per node list."""
 
