@@ -228,6 +228,8 @@ SIGNATURES = {
                                      _sz, _vp]),
     "ctgcn_lstm_cell_fwd_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ctgcn_lstm_cell_bwd_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "ctgcn_gru_cell_fwd_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
+    "ctgcn_gru_cell_bwd_f32": (_int, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ctgcn_spmm_csr_f64": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _int, _vp]),
     "ctgcn_tsgemm_tn_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "ctgcn_tsgemm_tn_f64": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),

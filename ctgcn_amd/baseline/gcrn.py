@@ -3,7 +3,8 @@ constructor, forward signature and state_dict keys of the reference's baseline/g
 
 Snapshot t goes through its own GCN (baseline/gcn.py); the row normalisation the reference applies to its output is the epilogue of
 layer 2's aggregation (ops.GCN_EPI_L2NORM).  LayerNorm(RNN(seq)) over the [N, T, output_dim] sequence is layers.rnn_reduce_norm: the
-fused GRU kernels (forward, and the step-wise backward) at output_dim 128, the fused LSTM recurrence for inference, the torch modules otherwise.
+fused GRU / LSTM kernels (forward, and the step-wise backward) at output_dim 128, library GEMMs plus one fused cell pass per step
+(ops.gru_layer / ops.lstm_layer) at any other width.
 Without grad the snapshots' rows are written straight into the sequence buffer.
 """
 import torch

@@ -5,7 +5,7 @@ import subprocess
 import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = [os.path.join(_HERE, "csrc", f) for f in ("ctgcn_hip.hip", "ctgcn_gemm.hip", "ctgcn_gru_bwd.hip", "ctgcn_ingest.hip", "ctgcn_walks.hip", "ctgcn_epoch.hip", "ctgcn_eval.hip", "ctgcn_cent.hip", "ctgcn_nodecls.hip", "ctgcn_sim.hip", "ctgcn_supervised.hip", "ctgcn_gcn.hip", "ctgcn_gat.hip", "ctgcn_pool.hip", "ctgcn_tg.hip", "ctgcn_pgnn.hip", "ctgcn_vgrnn.hip", "ctgcn_dyngem.hip", "ctgcn_lstmcell.hip", "ctgcn_timers.hip", "ctgcn_export.cpp")]
+SRCS = [os.path.join(_HERE, "csrc", f) for f in ("ctgcn_hip.hip", "ctgcn_gemm.hip", "ctgcn_gru_bwd.hip", "ctgcn_ingest.hip", "ctgcn_walks.hip", "ctgcn_epoch.hip", "ctgcn_eval.hip", "ctgcn_cent.hip", "ctgcn_nodecls.hip", "ctgcn_sim.hip", "ctgcn_supervised.hip", "ctgcn_gcn.hip", "ctgcn_gat.hip", "ctgcn_pool.hip", "ctgcn_tg.hip", "ctgcn_pgnn.hip", "ctgcn_vgrnn.hip", "ctgcn_dyngem.hip", "ctgcn_lstmcell.hip", "ctgcn_grucell.hip", "ctgcn_timers.hip", "ctgcn_export.cpp")]
 HDR = os.path.join(os.path.dirname(_HERE), "include", "ctgcn_hip.h")
 OUT = os.path.join(_HERE, "csrc", "libctgcn_hip.so")
 STAMP = OUT + ".srchash"          # sha256 of the sources + header + this recipe the .so was built from (travels with it, git-ignored)

@@ -3,7 +3,8 @@
 
 The aggregation (reference layers.py:41-48 + the stack/transpose of :58) runs in ctgcn_core_aggregate_f32; the
 core-axis GRU/LSTM + sum over cores + LayerNorm (layers.py:59-62) in the fused recurrence kernels when hidden = 128
-(ops.gru_sequence / ops.lstm_sequence), otherwise in the PyTorch-ROCm modules, chunked over rows.
+(ops.gru_sequence / ops.lstm_sequence), at other widths in library GEMMs plus one fused HIP cell pass per step (ops.gru_layer /
+ops.lstm_layer), and otherwise (several layers, bidirectional, proj_size) in the PyTorch-ROCm modules, chunked over rows.
 """
 import torch
 from torch import nn
@@ -17,9 +18,11 @@ _RNN_MAX_ELEMS = 1 << 29     # MIOpen's RNN indexes its gate workspace with 32-b
 
 
 def rnn_reduce_norm(rnn, norm, seq, reduce_sum, out=None, resident_backward=True):
-    """norm(rnn(seq).sum(1)) or norm(rnn(seq)).  GRU(hidden=128): fused HIP kernels, forward and backward.
-    LSTM(hidden=128): fused HIP recurrence for inference.  Everything else (other widths, LSTM training) goes through
-    the PyTorch-ROCm modules.  out (inference only, reduce_sum): a [rows, hidden] strided view that receives the result.
+    """norm(rnn(seq).sum(1)) or norm(rnn(seq)).  GRU(hidden=128) and LSTM(hidden=128): fused HIP kernels, forward and backward.
+    A single-layer, unidirectional, batch_first GRU of any other width, or such an LSTM without projection: library GEMMs and one
+    fused HIP cell pass per step (ops.gru_layer / ops.lstm_layer, forward and backward), then norm as a torch module; CTGCN_RNN_CELL=0
+    sends these to the PyTorch-ROCm modules instead.  Everything else (several layers, bidirectional, proj_size) goes through the
+    PyTorch-ROCm modules.  out (inference only, reduce_sum): a [rows, hidden] strided view that receives the result.
     resident_backward: see ops.gru_sequence (GCRN passes False)."""
     if out is not None and torch.is_grad_enabled() and (seq.requires_grad or any(p.requires_grad for p in rnn.parameters())):
         out = None                                   # training: autograd needs its own tensors
@@ -29,12 +32,31 @@ def rnn_reduce_norm(rnn, norm, seq, reduce_sum, out=None, resident_backward=True
         res = ops.gru_sequence(rnn, seq, norm, reduce_sum, resident_backward=resident_backward)
     elif ops.lstm_fused_ok(rnn, seq):
         res = ops.lstm_sequence(rnn, seq, norm, reduce_sum)
+    elif ops.rnn_cell_ok(rnn, seq):
+        res = norm(rnn_cells_over_rows(rnn, seq, reduce_sum))
     else:
         res = norm(rnn_over_rows(rnn, seq, reduce_sum))
     if out is not None:
         out.copy_(res)
         return out
     return res
+
+
+def rnn_cells_over_rows(rnn, seq, reduce_sum):
+    """rnn(seq)[0], or its sum over the steps, for what ops.rnn_cell_ok admits: the GRU through ops.gru_layer, which chunks the rows
+    and sums inside its cell pass; the LSTM through ops.lstm_layer in row chunks of the same bound (ops._GI_MAX_ELEMS elements of
+    gates), summed chunk by chunk.  No MIOpen call, so its 2^31 limit plays no part."""
+    bias = lambda name: getattr(rnn, name) if rnn.bias else None  # noqa: E731
+    args = (rnn.weight_ih_l0, rnn.weight_hh_l0, bias("bias_ih_l0"), bias("bias_hh_l0"))
+    if isinstance(rnn, nn.GRU):
+        return ops.gru_layer(seq, *args, reduce_sum=reduce_sum)
+    rows, steps, _ = seq.shape
+    chunk = max(1, ops._GI_MAX_ELEMS // max(1, steps * 4 * rnn.hidden_size))
+    parts = []
+    for lo in range(0, max(rows, 1), chunk):
+        out = ops.lstm_layer(seq[lo:lo + chunk], *args)
+        parts.append(out.sum(dim=1) if reduce_sum else out)
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
 
 
 def rnn_over_rows(rnn, seq, reduce_sum):

@@ -3867,6 +3867,182 @@ def lstm_layer(x, weight_ih, weight_hh, bias_ih=None, bias_hh=None, last_only=Fa
                             train)
 
 
+# ------------------------------------------------------------------------- a GRU layer of any width (ctgcn_grucell.hip): rnn_reduce_norm
+def rnn_cell_enabled():
+    """CTGCN_RNN_CELL=0 sends the GRUs of widths other than 128 and the LSTMs the width-128 kernels do not take back to the PyTorch-ROCm
+    modules (layers.rnn_over_rows) for A/B measurement; default: library GEMMs plus one fused HIP cell pass per step."""
+    return _os.environ.get("CTGCN_RNN_CELL", "1") != "0"
+
+
+def rnn_cell_ok(rnn, seq):
+    """What ops.gru_layer / ops.lstm_layer run for layers.rnn_reduce_norm: an fp32 CUDA sequence through a single-layer, unidirectional,
+    batch_first nn.GRU of any hidden size other than 128 (that one has kernels of its own, gru_fused_ok) or nn.LSTM without projection."""
+    if not (seq.is_cuda and seq.dtype == torch.float32 and seq.dim() == 3 and rnn_cell_enabled()):
+        return False
+    if not isinstance(rnn, (torch.nn.GRU, torch.nn.LSTM)) or rnn.num_layers != 1 or rnn.bidirectional or not rnn.batch_first:
+        return False
+    if rnn.weight_hh_l0.dtype != torch.float32 or not rnn.weight_hh_l0.is_cuda:
+        return False
+    return rnn.hidden_size != 128 if isinstance(rnn, torch.nn.GRU) else getattr(rnn, "proj_size", 0) == 0
+
+
+def _gru_cell_fwd(gi_t, gh, b_hh, h_prev, h, gates, q, acc=None, acc_init=False):
+    lib = _lib.load()
+    B, H = h.shape
+    ld = lambda t: 0 if t is None else t.stride(0)  # noqa: E731
+    with torch.cuda.device(h.device), _timed("gru_cell_fwd", n=B, d=H):
+        check(lib.ctgcn_gru_cell_fwd_f32(B, H, ptr(gi_t), ld(gi_t), ptr(gh), ld(gh), ptr(b_hh), ptr(h_prev), ld(h_prev), ptr(h), ld(h), ptr(gates),
+                                         ld(gates), ptr(q), ld(q), ptr(acc), ld(acc), int(bool(acc_init)), _stream()), "ctgcn_gru_cell_fwd_f32")
+
+
+def _gru_cell_bwd(gates, q, h_prev, dh_out, dh_rec, dgi, dgh, dh_prev):
+    lib = _lib.load()
+    B, H = q.shape
+    ld = lambda t: 0 if t is None else t.stride(0)  # noqa: E731
+    with torch.cuda.device(q.device), _timed("gru_cell_bwd", n=B, d=H):
+        check(lib.ctgcn_gru_cell_bwd_f32(B, H, ptr(gates), ld(gates), ptr(q), ld(q), ptr(h_prev), ld(h_prev), ptr(dh_out), ld(dh_out),
+                                         ptr(dh_rec), ld(dh_rec), ptr(dgi), ld(dgi), ptr(dgh), ld(dgh), ptr(dh_prev), ld(dh_prev), _stream()),
+              "ctgcn_gru_cell_bwd_f32")
+
+
+class _GruLayer(torch.autograd.Function):
+    """Every per-step tensor is time-major, [L, B, .], as in _LstmLayer: a step is a contiguous [B, .] block for the GEMMs, and the steps
+    >= 1 of dgh and the steps < L - 1 of h are contiguous too, so dW_hh is one GEMM over them without a copy."""
+
+    @staticmethod
+    def forward(ctx, x, gi, w_ih, w_hh, b_ih, b_hh, reduce_sum, train):
+        H = w_hh.shape[1]
+        dev = w_hh.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        own = gi is None
+        if own:
+            xt = _time_major(x)
+            L, B = xt.shape[:2]
+            x2d = xt.reshape(L * B, -1)
+            with _timed("gru_layer_gemm", n=L * B, d=3 * H):
+                git = (torch.mm(x2d, w_ih.t()) if b_ih is None else torch.addmm(b_ih, x2d, w_ih.t())).view(L, B, 3 * H)
+        else:
+            xt = None
+            git = (gi if gi.stride(2) == 1 else gi.contiguous()).transpose(0, 1)
+            L, B = git.shape[:2]
+        gh = new(B, 3 * H) if L > 1 else None
+        w_hh_t = w_hh.t()
+        acc = new(B, H) if reduce_sum else None
+        if train:
+            # the activated gates take the memory of a gi made here (a step's kernel reads and writes each element once)
+            gates = git if own else new(L, B, 3 * H)
+            q_all = new(L, B, H)
+            h_all = new(L - 1 if reduce_sum else L, B, H)              # the backward reads h_t as step t + 1's h_prev: never h_{L-1}
+            h_last = new(B, H) if reduce_sum else h_all[L - 1]
+            for t in range(L):
+                if t:
+                    with _timed("gru_layer_gemm", n=B, d=3 * H):
+                        torch.mm(h_all[t - 1], w_hh_t, out=gh)
+                _gru_cell_fwd(git[t], gh if t else None, b_hh, h_all[t - 1] if t else None, h_last if t == L - 1 else h_all[t], gates[t],
+                              q_all[t], acc, t == 0)
+            ctx.save_for_backward(xt, w_ih, w_hh, gates, q_all, h_all)
+            ctx.own, ctx.reduce_sum, ctx.has_bias = own, reduce_sum, (b_ih is not None, b_hh is not None)
+        else:
+            h_all = new(2 if reduce_sum else L, B, H)
+            for t in range(L):
+                h_t, h_p = (h_all[t & 1], h_all[(t - 1) & 1]) if reduce_sum else (h_all[t], h_all[t - 1])
+                if t:
+                    with _timed("gru_layer_gemm", n=B, d=3 * H):
+                        torch.mm(h_p, w_hh_t, out=gh)
+                _gru_cell_fwd(git[t], gh if t else None, b_hh, h_p if t else None, h_t, None, None, acc, t == 0)
+        return acc if reduce_sum else h_all.transpose(0, 1)
+
+    @staticmethod
+    def backward(ctx, dout):
+        xt, w_ih, w_hh, gates, q_all, h_all = ctx.saved_tensors
+        L, B, H3 = gates.shape
+        H = H3 // 3
+        dev = gates.device
+        if dout.dtype != torch.float32 or dout.stride(-1) != 1 or dout.stride(0) < H:           # an expanded gradient has stride 0
+            dout = dout.to(torch.float32).contiguous()
+        dgi = torch.empty(L, B, H3, dtype=torch.float32, device=dev)
+        dgh = torch.empty(L, B, H3, dtype=torch.float32, device=dev)
+        dh_rec = torch.empty(B, H, dtype=torch.float32, device=dev) if L > 1 else None
+        for t in range(L - 1, -1, -1):
+            # dh_rec is read as the complete dh of this step and takes the direct part dh z of dh_prev, written by the same thread;
+            # the GEMM then adds dgh_t W_hh to it
+            _gru_cell_bwd(gates[t], q_all[t], h_all[t - 1] if t else None, dout if ctx.reduce_sum else dout[:, t], None if t == L - 1 else dh_rec,
+                          dgi[t], dgh[t], dh_rec if t else None)
+            if t:
+                with _timed("gru_layer_gemm", n=B, d=H):
+                    dh_rec.addmm_(dgh[t], w_hh)
+        need = ctx.needs_input_grad
+        dgi2 = dgi.view(L * B, H3)
+        dx = dgi_out = dw_ih = dw_hh = db_ih = db_hh = None
+        if ctx.has_bias[0] and need[4]:
+            db_ih = dgi2.sum(0)
+        if ctx.has_bias[1] and need[5]:
+            db_hh = dgh.view(L * B, H3).sum(0)                         # differs from db_ih in the n block: da_n r
+        with _timed("gru_layer_gemm", n=L * B, d=H3):
+            if need[3]:
+                dw_hh = torch.mm(dgh[1:].reshape((L - 1) * B, H3).t(), h_all[:L - 1].reshape((L - 1) * B, H)) if L > 1 else torch.zeros_like(w_hh)
+            if ctx.own:
+                x2d = xt.reshape(L * B, -1)
+                if need[2]:
+                    dw_ih = torch.mm(dgi2.t(), x2d)
+                if need[0]:
+                    dx = torch.mm(dgi2, w_ih).view(L, B, -1).transpose(0, 1)
+            elif need[1]:
+                dgi_out = dgi.transpose(0, 1)
+        return dx, dgi_out, dw_ih, dw_hh, db_ih, db_hh, None, None
+
+
+def gru_layer(x, weight_ih, weight_hh, bias_ih=None, bias_hh=None, reduce_sum=False, gi=None):
+    """One batch_first nn.GRU layer of any hidden width H, zero initial state: h_seq [B, L, H], or with reduce_sum the sum of h over the
+    steps [B, H].  x [B, L, in] is dense; or gi [B, L, 3 H] is the input projection made elsewhere (bias_ih folded by its maker; x,
+    weight_ih and bias_ih are then None).  The parameters are those of the nn.GRU (gate order r, z, n); either bias may be None.
+    Differentiable in every tensor argument.  One library GEMM makes gi for all steps, one per step >= 1 makes h_{t-1} W_hhᵀ, and one
+    ctgcn_gru_cell_fwd_f32 pass per step does the rest (with reduce_sum it also keeps the running sum); the backward is one
+    ctgcn_gru_cell_bwd_f32 pass and one dgh_t W_hh GEMM per step, then one GEMM each for dW_hh (over the stacked steps >= 1), dW_ih and
+    dx, and the column sums of dgi (db_ih) and dgh (db_hh: they differ in the n block).
+    A training call keeps 5 H floats per (row, step) besides x: the activated gates r, z, n (in the memory of gi), q = h_{t-1} W_hnᵀ +
+    b_hn and h; its backward holds another 6 H (dgi and dgh) while it runs.  Without grad nothing per step is kept: h alternates between
+    two buffers with reduce_sum (else it is the output), and gi is the only [rows, L, 3 H] buffer.  Rows go through in equal chunks of
+    at most _GI_MAX_ELEMS / (3 H L) rows, so that buffer never exceeds _GI_MAX_ELEMS elements; rows are independent sequences, so the
+    chunks are exact.  h_seq of an unchunked call is a [B, L, H] view of [L, B, H] memory, which a following layer takes as it is."""
+    _need_cuda(x, gi, weight_ih, weight_hh, bias_ih, bias_hh)
+    if (x is None) == (gi is None):
+        raise ValueError("exactly one of x and gi expected")
+    if gi is not None and (weight_ih is not None or bias_ih is not None):
+        raise ValueError("with gi, weight_ih and bias_ih belong to whoever made it")
+    for t in (x, gi, weight_ih, weight_hh, bias_ih, bias_hh):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("fp32 tensors expected, got %s" % t.dtype)
+    if weight_hh.dim() != 2 or weight_hh.shape[0] != 3 * weight_hh.shape[1] or weight_hh.shape[1] < 1:
+        raise ValueError("weight_hh must be [3 H, H]")
+    H = weight_hh.shape[1]
+    seq = x if gi is None else gi
+    if seq.dim() != 3 or seq.shape[1] < 1:
+        raise ValueError("%s must be [B, L, %s] with L >= 1" % (("x", "in") if gi is None else ("gi", "3 H")))
+    if gi is None:
+        if weight_ih is None or weight_ih.dim() != 2 or tuple(weight_ih.shape) != (3 * H, x.shape[2]):
+            raise ValueError("weight_ih must be [%d, %d]" % (3 * H, x.shape[2]))
+    elif gi.shape[2] != 3 * H:
+        raise ValueError("gi must be [B, L, %d], got %s" % (3 * H, tuple(gi.shape)))
+    for b in (bias_ih, bias_hh):
+        if b is not None and tuple(b.shape) != (3 * H,):
+            raise ValueError("a bias must be [%d]" % (3 * H))
+    for t in (seq, weight_ih, bias_ih, bias_hh):
+        if t is not None and t.device != weight_hh.device:
+            raise ValueError("tensors on %s and %s" % (t.device, weight_hh.device))
+    train = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, gi, weight_ih, weight_hh, bias_ih, bias_hh))
+    bias_hh = None if bias_hh is None else (bias_hh if bias_hh.is_contiguous() else bias_hh.contiguous())
+    w_ih, w_hh = None if weight_ih is None else _row_view(weight_ih), _row_view(weight_hh)
+    rows, L = seq.shape[:2]
+    run = lambda part: _GruLayer.apply(part if gi is None else None, None if gi is None else part, w_ih, w_hh, bias_ih, bias_hh,  # noqa: E731
+                                       bool(reduce_sum), train)
+    max_rows = max(1, _GI_MAX_ELEMS // (3 * H * L))
+    if rows <= max_rows:
+        return run(seq)
+    chunk = -(-rows // -(-rows // max_rows))
+    return torch.cat([run(seq[lo:lo + chunk]) for lo in range(0, rows, chunk)], 0)
+
+
 # ------------------------------------------------------------------------------------- fp64 blocks (ctgcn_timers.hip)
 def _f64_block(t, what):
     if t.dtype != torch.float64 or t.dim() != 2:

@@ -1255,6 +1255,35 @@ int ctgcn_lstm_cell_bwd_f32(int64_t B, int32_t H, const float *gates, int64_t ld
                             int64_t ldcp, const float *dh_out, int64_t lddo, const float *dh_rec, int64_t lddr, const float *dc_next,
                             int64_t lddn, float *dgates, int64_t lddg, float *dc_prev, int64_t lddp, void *stream);
 
+/* ---- one time step of a GRU layer of any width (ctgcn_grucell.hip; ops.gru_layer: the core-axis and the temporal RNN of CTGCN, CGCN
+ * and GCRN at hidden widths other than 128).  The products with W_ih and W_hh are the caller's GEMMs; these are the element-wise
+ * passes between them.  B rows of hidden width H; a gate operand is [B, 3 H] in torch's order r, z, n, a state operand [B, H]; every
+ * operand has its own row stride, so a step may be a slice of a [B, L, .] or [L, B, .] tensor.
+ * ctgcn_gru_cell_fwd_f32: r = σ(gi_r + gh_r + b_hr), z = σ(gi_z + gh_z + b_hz), q = gh_n + b_hn, n = tanh(gi_n + r q),
+ *   h = (1 − z) n + z h_prev.  gi = x W_ihᵀ + b_ih and gh = h_prev W_hhᵀ come from the caller; gh null: no recurrent term (step 0,
+ *   h_{-1} = 0); b_hh [3 H] or null; h_prev null: zero.  Writes h and, unless gates and q are both null (inference), the activated
+ *   gates (r, z, n) [B, 3 H] and q [B, H]: what the backward reads.  acc not null: the running sum over the steps, acc = h with
+ *   acc_init != 0 (the first step: acc's old contents are not read) and acc += h otherwise.  gates may be gi itself and h may be
+ *   h_prev itself; acc and q are memory of their own.
+ * ctgcn_gru_cell_bwd_f32: from the saved gates and q of the step and h_prev (null at step 0: zero), with dh = dh_out + dh_rec (the
+ *   gradient from above, and the complete dh_prev of step t + 1; either may be null), dn = dh (1 − z), dz = dh (h_prev − n),
+ *   da_n = dn (1 − n²), da_z = dz z (1 − z), da_r = da_n q r (1 − r): writes dgi = (da_r, da_z, da_n), unless dgh is null
+ *   dgh = (da_r, da_z, da_n r), and unless dh_prev is null the direct part dh z of dh_prev; the caller's GEMM adds dgh W_hh to it.
+ *   dh_prev may be dh_rec itself, and dgi may be gates itself (when the saved gates are not needed again).
+ * Every element of every operand is read once and written once.  16-byte accesses when H and every row stride are multiples of 4
+ * and every base is 16-byte aligned (the float4 rule of the gathers), scalar ones otherwise; 64-bit element indices; no LDS, no
+ * atomics, repeated calls are bit-identical; σ and tanh are exact at saturation (0, 1, ±1 for |z| >= 100, never NaN).
+ * Returns CTGCN_E_INVALID for B outside [0, 2^31), H outside [1, 2^29), a row stride below the operand's width, a null gi, h
+ * (forward) or gates, q, dgi (backward), and gates without q or q without gates (forward); B = 0 returns CTGCN_OK before any pointer
+ * check.
+ */
+int ctgcn_gru_cell_fwd_f32(int64_t B, int32_t H, const float *gi, int64_t ldgi, const float *gh, int64_t ldgh, const float *b_hh,
+                           const float *h_prev, int64_t ldhp, float *h, int64_t ldh, float *gates, int64_t ldg, float *q, int64_t ldq,
+                           float *acc, int64_t ldacc, int32_t acc_init, void *stream);
+int ctgcn_gru_cell_bwd_f32(int64_t B, int32_t H, const float *gates, int64_t ldg, const float *q, int64_t ldq, const float *h_prev,
+                           int64_t ldhp, const float *dh_out, int64_t lddo, const float *dh_rec, int64_t lddr, float *dgi, int64_t lddgi,
+                           float *dgh, int64_t lddgh, float *dh_prev, int64_t lddp, void *stream);
+
 /* ---- the fp64 linear algebra of the TIMERS baseline (ctgcn_timers.hip; reference baseline/timers.py): the passes of a block
  * eigensolver on a CSR operator (ops.sym_topk), the edge-gather loss, TRIP and the restart bound.  Everything is double, row-major
  * with leading dimensions in elements; CSR as in ctgcn_spmm_csr_f32 (int32 row_ptr[n + 1] and col).
