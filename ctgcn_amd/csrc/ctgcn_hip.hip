@@ -5141,6 +5141,35 @@ int ctgcn_gru_weight_grad_f32(int64_t rows, int32_t steps, int32_t hidden, const
     if (rows < 0 || steps < 1 || ldg01 < 2 * GRU_H || ldg2 < GRU_H || ldx < GRU_H) return fail(CTGCN_E_INVALID, "gru_weight_grad: bad sizes");
     if (n_pairs < 8 || (n_pairs % 8)) return fail(CTGCN_E_INVALID, "gru_weight_grad: n_pairs=%d must be a positive multiple of 8", n_pairs);
     if (!partial || (rows > 0 && (!g01 || !g2 || !x))) return fail(CTGCN_E_INVALID, "gru_weight_grad: null pointer");
+    // gru_dw_x3_kernel reads every operand through one buffer descriptor per block (base = the block's first row, range clamped to
+    // 0x7fffffff bytes) and 32-bit byte offsets (row * ld + column) * 4 that advance by 32 rows per chunk.  A block pair owns
+    // `per` consecutive chunks; the three blocks that matter are the first (most rows, no row before it), the second (most rows behind
+    // a one-row `back` of the shifted operand) and the last (rows past the end, which must read as zero).  For each, the last row
+    // that holds data must end (its 32-column tail included: 128 bytes) inside the clamped range, and the last row of the final chunk
+    // - data or not - must keep its offset below 2^32, or it wraps back into the range and reads a row instead of zero.
+    {
+        const int64_t nchunks = (rows + DW_KB - 1) / DW_KB, per = (nchunks + n_pairs - 1) / n_pairs;
+        const int64_t nblk = per ? (nchunks + per - 1) / per : 0;
+        const struct { const char *name; int64_t ld; int sh; } ops3[3] = {{"g01", ldg01, 0}, {"g2", ldg2, 0}, {"x", ldx, shift_steps ? 1 : 0}};
+        for (const auto &o : ops3) {
+            int64_t data_rows = 0, pad_rows = 0;       // largest row offset from a descriptor's base: rows that hold data / any staged row
+            const int64_t blk[3] = {0, 1, nblk - 1};
+            for (int64_t p : blk) {
+                if (p < 0 || p >= nblk) continue;
+                const int64_t row_lo = p * per * DW_KB, row_hi = std::min((p + 1) * per, nchunks) * DW_KB;     // the block's staged rows
+                const int64_t first = row_lo - (row_lo >= o.sh ? o.sh : 0);                                     // descriptor base row
+                data_rows = std::max(data_rows, std::min(row_hi, rows) - 1 - o.sh - first);
+                pad_rows = std::max(pad_rows, row_hi - 1 - o.sh - first);
+            }
+            const int64_t lim_data = data_rows > 0 ? (0x7fffffffLL - 128) / 4 / data_rows : INT64_MAX;
+            const int64_t lim_pad = pad_rows > data_rows ? (0x100000000LL - 128) / 4 / pad_rows : INT64_MAX;
+            const int64_t max_ld = std::min(lim_data, lim_pad);
+            if (o.ld > max_ld)
+                return fail(CTGCN_E_UNSUPPORTED, "gru_weight_grad: %s with ld=%lld: a block's %lld rows span more than its 2 GiB descriptor "
+                            "(32-bit offsets); largest usable ld for rows=%lld, n_pairs=%d is %lld, or raise n_pairs", o.name, (long long)o.ld,
+                            (long long)(pad_rows + 1), (long long)rows, n_pairs, (long long)max_ld);
+        }
+    }
     DwArgs a{};
     a.rows = rows; a.steps = steps; a.shift = shift_steps ? 1 : 0; a.g01 = g01; a.ldg01 = ldg01; a.g2 = g2; a.ldg2 = ldg2;
     a.x = x; a.ldx = ldx; a.partial = partial; a.pairs = n_pairs; a.accumulate = accumulate ? 1 : 0;

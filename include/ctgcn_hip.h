@@ -516,6 +516,15 @@ int ctgcn_gru_input_grad_f32(int64_t rows, int32_t d_in, int32_t hidden, const f
  * accumulate != 0 adds to `partial` instead of overwriting it (one host-side sum after many calls).
  * rows = nodes * steps.  n_pairs: a positive multiple of 8 (half the CU count uses the whole device).  Split-bf16
  * arithmetic, deterministic.
+ * Stride limit (CTGCN_E_UNSUPPORTED, nothing launched; ctgcn_last_error() names the operand and its largest usable ld): the kernel
+ * reads each operand through one buffer descriptor per block — base = the block's first row, range clamped to 0x7fffffff bytes —
+ * and 32-bit byte offsets.  Block pair p stages the 32-row chunks [p per, (p + 1) per), per = ceil(ceil(rows / 32) / n_pairs); the
+ * shifted x is read from one row before the block's first (row - 1 of the matrix is never read).  With m the largest distance in
+ * rows from a block's base to a row that holds data, (m ld + 32) · 4 <= 0x7fffffff must hold for ldg01, ldg2 and ldx alike (the
+ * 32 is the column tail of the widest load); and when rows is no multiple of 32, the last staged row m' of the final chunk needs
+ * (m' ld + 32) · 4 <= 2^32, so that its offset does not wrap back into the range and it reads as zero.  Full blocks have
+ * m = 32 per - 1: a dense 384-wide d_gi with n_pairs = 8 reaches the limit at about 11 M rows, with the 128 pairs of an MI355X
+ * at about 180 M; more pairs shorten the spans.
  */
 int ctgcn_gru_weight_grad_f32(int64_t rows, int32_t steps, int32_t hidden, const float *g01, int64_t ldg01, const float *g2,
                               int64_t ldg2, const float *x, int64_t ldx, int shift_steps, float *partial, int32_t n_pairs,
