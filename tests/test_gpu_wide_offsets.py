@@ -52,6 +52,7 @@ TABLE = {
     "ctgcn_gru_input_proj_f32": _row({"ldx": ALIGNED}, drive="ops._project"),
     "ctgcn_gru_input_grad_f32": _row({"ldx": ALIGNED}, drive="ops._project_grad"),
     "ctgcn_gru_weight_grad_f32": _row({"ldg01": BOTH, "ldg2": BOTH, "ldx": BOTH}, drive="ops._weight_grad"),
+    "ctgcn_gru_bwd_in_f32": _row({"ldx": ALIGNED}),          # an ldx that is no multiple of 4 is refused by contract
     "ctgcn_linear_f32": _row({"ldx": BOTH, "ldw": BOTH, "ldy": BOTH}),
     "ctgcn_split_rows_f32": _row({"ldx": BOTH}),
     "ctgcn_pack_weight_f32": _row({"ldw": BOTH}),
@@ -105,7 +106,6 @@ TABLE = {
     "ctgcn_tsgemm_nn_f64": _row({"ldx": ALIGNED, "ldc": ALIGNED, "ldy": ALIGNED}),
     "ctgcn_timers_obj_f64": _row({"ldu": ALIGNED, "ldv": ALIGNED}),
     # ------------------------------------------------------------------------------------------ listed, not driven yet
-    "ctgcn_gru_bwd_in_f32": _todo("not driven yet: needs the saved gates and d_gi of the fused training chain as fixture", "ldx"),
     "ctgcn_transpose_bias_group_f32": _todo("not driven yet: grouped call (descriptor table + host pointer arrays); same kernel body as ctgcn_transpose_bias_f32", "ldw", "ldo"),
     "ctgcn_linear_packed_group_f32": _todo("not driven yet: grouped call over whole 128-row panels: a wide y needs 128 rows, the layouts hold 33", "ldy"),
     "ctgcn_negsampling_loss_fwd_bwd_f32": _todo("not driven yet: needs the exact sampler model of tests/_sampling_ref.py to build its index arrays", "lde", "ldg"),
@@ -561,6 +561,32 @@ def _drive_gru_input_grad(arena, param, layout):
         ops._project_grad(g, w, t["dx"])
 
     _run_case(arena, layout, "dx", {}, {"dx": (N, 128)}, call, {"dx": g.double().cpu() @ w.double().cpu()}, _split_close(g, w))
+
+
+GRU_BWD_IN_CASE = dict(rows=11, steps=3, mask_bits=[0b101], seed=90)      # audited by tests/test_gru_bwd_ref_host.py
+
+
+def _drive_gru_bwd_in(arena, param, layout):
+    """tests/test_gpu_gru_bwd_direct.py's exact tier: 11 sequences of 3 steps = 33 row-steps of fp32 x, one per wide row, under a row plan;
+    d_gi and x are NaN at the steps that are not fresh, dx keeps its prefill there.  Bit for bit the float64 model."""
+    import _gru_bwd_ref as M
+    lib = _lib()
+    rows, steps, bits = GRU_BWD_IN_CASE["rows"], GRU_BWD_IN_CASE["steps"], GRU_BWD_IN_CASE["mask_bits"]
+    assert rows * steps == N
+    t, want = M.exact_case(audit=False, **GRU_BWD_IN_CASE)
+    fresh = M.fresh_matrix(bits, rows, steps)
+    x = torch.from_numpy(np.where(fresh[:, :, None], t["x"], np.nan).reshape(N, 128)).float().to(DEV)
+    dgi, w_ih = torch.from_numpy(want["d_gi"]).float().to(DEV), torch.from_numpy(t["w_ih"]).float().to(DEV)
+    tm = torch.from_numpy(M.pack_masks(bits, steps).view(np.int32)).to(DEV)
+    assert lib.ctgcn_gru_bwd_blocks(rows) == 1
+
+    def call(v):
+        _ck(lib.ctgcn_gru_bwd_in_f32(rows, steps, 128, _p(dgi), _p(w_ih), _p(tm), None, 0, 0, _p(v["x"]), v["x"].stride(0), _p(v["dx"]), None, None,
+                                     None, 0, _p(v["dw"]), _p(v["dbi"]), 1, 0, _stream()), "ctgcn_gru_bwd_in_f32")
+
+    ref = {"dx": torch.from_numpy(np.nan_to_num(want["dx"], nan=W.SENTINEL).reshape(N, 128)), "dw": torch.from_numpy(want["dW_ih"]),
+           "dbi": torch.from_numpy(want["db_ih"][None])}
+    _run_case(arena, layout, "x", {"x": x}, {"dx": (N, 128), "dw": (384, 128), "dbi": (1, 384)}, call, ref, _exact)
 
 
 # ------------------------------------------------------------------------------------------------------- the split GEMM
@@ -1655,6 +1681,7 @@ DRIVERS = {
     "ctgcn_gru_input_proj_f32": _drive_gru_input_proj,
     "ctgcn_gru_input_grad_f32": _drive_gru_input_grad,
     "ctgcn_gru_weight_grad_f32": _drive_weight_grad,
+    "ctgcn_gru_bwd_in_f32": _drive_gru_bwd_in,
     "ctgcn_linear_f32": _drive_linear,
     "ctgcn_split_rows_f32": _drive_packed("split_rows"),
     "ctgcn_pack_weight_f32": _drive_packed("pack_weight"),
