@@ -49,6 +49,7 @@ SIGNATURES = {
     "ctgcn_hub_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "ctgcn_hub_split_entries": (_i32, []),
     "ctgcn_core_aggregate_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _u32, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "ctgcn_core_aggregate_bias_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "ctgcn_core_aggregate_bwd_prep_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _u32, _vp]),
     "ctgcn_core_aggregate_bwd_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _u32, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "ctgcn_edges_to_csr": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(_i64), _vp, _sz, _vp]),
@@ -81,6 +82,7 @@ SIGNATURES = {
     "ctgcn_linear_f32": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _sz, _vp]),
     "ctgcn_core_aggregate_split_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
     "ctgcn_core_aggregate_split_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _u32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _sz, _vp, _sz, _vp]),
+    "ctgcn_core_aggregate_split_bias_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _sz, _vp, _sz, _vp]),
     "ctgcn_gru_layer_presplit_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_float, _vp, _i64, _vp, _vp, _vp]),
     "ctgcn_linear_presplit_f32": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp]),
     "ctgcn_gru_seq_bwd_f32": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _int, _vp]),

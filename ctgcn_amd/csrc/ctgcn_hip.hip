@@ -106,13 +106,17 @@ struct AggArgs {
     // tbase[T] + (p % 64) popcount(mask); the GEMM then runs over the compact rows only.  tbase null: rows p K + slot (holes).
     int32_t tile_shift;
     const int32_t *tbase;
+    // forward kernels, BIAS instantiations only: every operand row a kernel reads (gathered neighbour rows and the row's own self-loop
+    // row) is src[row] + gather_bias as ONE fp32 add before the multiply-accumulate — the rows of Linear(one-hot) = W^T + b read from the
+    // weight itself, bit for bit what transpose_bias_kernel would have materialised.  Null: the non-BIAS instantiations, src as it is.
+    const float *gather_bias;
 };
 
 // ------------------------------------------------------------------------------------------------
 // forward: per row   R = [self] X[row];  for slot j: P (+)= sum_{e in slot j} val*X[col];  R += P;
 //                    out[row, j] = relu?(R)
 // ------------------------------------------------------------------------------------------------
-template <int VEC, int LPR, int U>
+template <int VEC, int LPR, int U, bool BIAS = false>      // BIAS: operand rows are src[row] + gather_bias (AggArgs); its own instantiation
 __global__ __launch_bounds__(256) void agg_fwd_kernel(const AggArgs a)
 {
     using V = typename vec_of<VEC>::type;
@@ -134,7 +138,12 @@ __global__ __launch_bounds__(256) void agg_fwd_kernel(const AggArgs a)
         // dead lanes read chunk 0 (valid memory) and never store: keeps every load unconditional
         const int64_t foff = live ? (int64_t)ch * VEC : 0;
         V R = vzero<VEC>(), P = vzero<VEC>();
-        if (self) R = *(const V *)(X + row * a.ldsrc + foff);
+        V bv = vzero<VEC>();
+        if constexpr (BIAS) bv = *(const V *)(a.gather_bias + foff);
+        if (self) {
+            R = *(const V *)(X + row * a.ldsrc + foff);
+            if constexpr (BIAS) R += bv;
+        }
         int cur = 0;
 
         auto close_slot = [&]() {
@@ -174,6 +183,7 @@ __global__ __launch_bounds__(256) void agg_fwd_kernel(const AggArgs a)
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     while (cur < sj[u]) close_slot();
+                    if constexpr (BIAS) xv[u] += bv;
                     P = vfma(wj[u], xv[u], P);
                 }
             }
@@ -181,8 +191,9 @@ __global__ __launch_bounds__(256) void agg_fwd_kernel(const AggArgs a)
                 const int cj = __shfl(c, j, LPR);
                 const float w1 = __shfl(w, j, LPR);
                 const int s1 = __shfl(s, j, LPR);
-                const V x1 = *(const V *)(X + (int64_t)cj * a.ldsrc + foff);
+                V x1 = *(const V *)(X + (int64_t)cj * a.ldsrc + foff);
                 while (cur < s1) close_slot();
+                if constexpr (BIAS) x1 += bv;
                 P = vfma(w1, x1, P);
             }
         }
@@ -262,7 +273,7 @@ __host__ __device__ __forceinline__ int hub_pieces(int len, int max_pieces)
     return np < 1 ? 1 : (np > max_pieces ? max_pieces : np);
 }
 
-template <int VEC, int LPR, int U>
+template <int VEC, int LPR, int U, bool BIAS = false>
 __global__ __launch_bounds__(HUB_THREADS) void agg_fwd_hub_kernel(const AggArgs a)
 {
     using V = typename vec_of<VEC>::type;
@@ -292,6 +303,8 @@ __global__ __launch_bounds__(HUB_THREADS) void agg_fwd_hub_kernel(const AggArgs 
         const int ch = pass * LPR + lig;
         const bool live = ch < a.chunks;
         const int64_t foff = live ? (int64_t)ch * VEC : 0;
+        V bv = vzero<VEC>();
+        if constexpr (BIAS) bv = *(const V *)(a.gather_bias + foff);
         if (grp < G) {
             for (int k = 0; k < a.K; ++k) part[((int64_t)grp * a.K + k) * LPR + lig] = vzero<VEC>();
             V P = vzero<VEC>();
@@ -321,6 +334,7 @@ __global__ __launch_bounds__(HUB_THREADS) void agg_fwd_hub_kernel(const AggArgs 
                             P = vzero<VEC>();
                             cur = sj[u];
                         }
+                        if constexpr (BIAS) xv[u] += bv;
                         P = vfma(wj[u], xv[u], P);
                     }
                 }
@@ -328,12 +342,13 @@ __global__ __launch_bounds__(HUB_THREADS) void agg_fwd_hub_kernel(const AggArgs 
                     const int cj = __shfl(c, j, LPR);
                     const float w1 = __shfl(w, j, LPR);
                     const int s1 = __shfl(s, j, LPR);
-                    const V x1 = *(const V *)(X + (int64_t)cj * a.ldsrc + foff);
+                    V x1 = *(const V *)(X + (int64_t)cj * a.ldsrc + foff);
                     if (s1 != cur) {
                         if (cur >= 0) part[((int64_t)grp * a.K + cur) * LPR + lig] = P;
                         P = vzero<VEC>();
                         cur = s1;
                     }
+                    if constexpr (BIAS) x1 += bv;
                     P = vfma(w1, x1, P);
                 }
             }
@@ -353,7 +368,10 @@ __global__ __launch_bounds__(HUB_THREADS) void agg_fwd_hub_kernel(const AggArgs 
         }
         if (grp == 0) {
             V R = vzero<VEC>(), Pc = vzero<VEC>();
-            if (self) R = *(const V *)(X + row * a.ldsrc + foff);
+            if (self) {
+                R = *(const V *)(X + row * a.ldsrc + foff);
+                if constexpr (BIAS) R += bv;
+            }
             for (int k = 0; k < a.K; ++k) {
                 V sk = vzero<VEC>();
                 for (int g = 0; g < G; ++g) sk += part[((int64_t)g * a.K + k) * LPR + lig];
@@ -457,7 +475,7 @@ __global__ __launch_bounds__(HUB_THREADS) void agg_bwd_hub_kernel(const AggArgs 
 
 // Second pass for hub rows cut into pieces: one small block per hub row adds the pieces' partial sums in piece order and runs the
 // row's R/P recurrence (forward) / adds the self term (backward).  Deterministic: fixed piece boundaries, fixed order.
-template <int VEC, bool FWD>
+template <int VEC, bool FWD, bool BIAS = false>
 __global__ __launch_bounds__(256) void agg_hub_final_kernel(const AggArgs a)
 {
     using V = typename vec_of<VEC>::type;
@@ -472,7 +490,10 @@ __global__ __launch_bounds__(256) void agg_hub_final_kernel(const AggArgs a)
         if (FWD) {
             float *__restrict__ outrow = a.out + (a.hub_compact ? (int64_t)hub : row) * a.out_ld;
             V R = vzero<VEC>(), Pc = vzero<VEC>();
-            if (self) R = *(const V *)(a.src + row * a.ldsrc + foff);
+            if (self) {
+                R = *(const V *)(a.src + row * a.ldsrc + foff);
+                if constexpr (BIAS) R += *(const V *)(a.gather_bias + foff);
+            }
             for (int k = 0; k < a.K; ++k) {
                 V sk = vzero<VEC>();
                 for (int p = 0; p < np; ++p) sk += *(const V *)(mine + ((int64_t)p * a.K + k) * a.hub_ld + foff);
@@ -557,14 +578,14 @@ int persistent_cus(int device_cus) { return g_persistent_cus > 0 && g_persistent
 
 constexpr size_t HUB_LDS_BUDGET = 144 * 1024;
 
-template <bool FWD, int VEC, int LPR>
+template <bool FWD, int VEC, int LPR, bool BIAS = false>
 void launch_agg_t(AggArgs a, hipStream_t st)
 {
     constexpr int U = 4;
     const int rows_per_block = 256 / LPR;
     const int64_t blocks = (a.n + rows_per_block - 1) / rows_per_block;
     if (FWD)
-        hipLaunchKernelGGL((agg_fwd_kernel<VEC, LPR, U>), dim3((unsigned)blocks), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((agg_fwd_kernel<VEC, LPR, U, BIAS>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL((agg_bwd_kernel<VEC, LPR, U>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     if (a.n_long > 0) {
@@ -575,14 +596,14 @@ void launch_agg_t(AggArgs a, hipStream_t st)
         const size_t lds = per_group * G;
         const unsigned hub_grid = (unsigned)a.n_long * (unsigned)(a.hub_part ? a.hub_split : 1);
         if (FWD) {
-            auto k = agg_fwd_hub_kernel<VEC, LPR, U>;
+            auto k = agg_fwd_hub_kernel<VEC, LPR, U, BIAS>;
             if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL(k, dim3(hub_grid), dim3(HUB_THREADS), lds, st, a);
         } else {
             auto k = agg_bwd_hub_kernel<VEC, LPR, U>;
             hipLaunchKernelGGL(k, dim3(hub_grid), dim3(HUB_THREADS), lds, st, a);
         }
-        if (a.hub_part) hipLaunchKernelGGL((agg_hub_final_kernel<VEC, FWD>), dim3((unsigned)a.n_long), dim3(256), 0, st, a);
+        if (a.hub_part) hipLaunchKernelGGL((agg_hub_final_kernel<VEC, FWD, BIAS>), dim3((unsigned)a.n_long), dim3(256), 0, st, a);
     }
 }
 
@@ -614,7 +635,7 @@ int launch_agg(AggArgs a, bool vec4_ok, hipStream_t st)
     if (a.n_long > 0 && (size_t)a.K * p.lpr * (p.vec * 4) > HUB_LDS_BUDGET) { a.n_long = 0; a.long_thresh = 0x7fffffff; }   // K*d too large for the LDS partials: rows stay on the normal path
     const int64_t rows_per_block = 256 / p.lpr;
     if ((a.n + rows_per_block - 1) / rows_per_block > 0x7fffffffLL) return fail(CTGCN_E_UNSUPPORTED, "grid too large");
-#define CASE(V, L) if (p.vec == V && p.lpr == L) { launch_agg_t<FWD, V, L>(a, st); }
+#define CASE(V, L) if (p.vec == V && p.lpr == L) { if (FWD && a.gather_bias) launch_agg_t<FWD, V, L, FWD>(a, st); else launch_agg_t<FWD, V, L>(a, st); }
     CASE(4, 8) else CASE(4, 16) else CASE(4, 32) else CASE(4, 64)
     else CASE(1, 8) else CASE(1, 16) else CASE(1, 32) else CASE(1, 64)
 #undef CASE
@@ -1759,7 +1780,8 @@ __device__ __forceinline__ float group_max(float m)       // m >= 0: its bit pat
 // 4 d bytes written instead of 4 d written + 4 d read + 4 d written, and one pass over the entries instead of d / 256.
 // ------------------------------------------------------------------------------------------------
 // WIDE (round 5): a row plan over 33-64 slots: two mask words per tile.  Separate instantiations: the K <= 32 kernels keep their code.
-template <int LPR, int CH, int U, bool WIDE = false>
+// BIAS: operand rows are src[row] + gather_bias (AggArgs); separate instantiations, the others keep their code.
+template <int LPR, int CH, int U, bool WIDE = false, bool BIAS = false>
 __device__ __forceinline__ void agg_fwd_split_body(const AggArgs &a, _Float16 *__restrict__ p1, _Float16 *__restrict__ p2,
                                                    float *__restrict__ scale, int32_t kp, float residual_scale, const int64_t bid)
 {
@@ -1793,13 +1815,19 @@ __device__ __forceinline__ void agg_fwd_split_body(const AggArgs &a, _Float16 *_
     bool live[CH];
     int64_t foff[CH];
     f4 R[CH], P[CH];
+    f4 bv[CH];                                        // BIAS: the lane's own columns of the bias
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
         const int ch = c * LPR + lig;
         live[c] = ch < a.chunks;
         foff[c] = live[c] ? (int64_t)ch * 4 : 0;      // dead lanes read chunk 0 (valid memory): every load unconditional
         R[c] = P[c] = vzero<4>();
-        if (self && live[c]) R[c] = *(const f4 *)(X + row * a.ldsrc + foff[c]);
+        bv[c] = vzero<4>();
+        if constexpr (BIAS) bv[c] = *(const f4 *)(a.gather_bias + foff[c]);
+        if (self && live[c]) {
+            R[c] = *(const f4 *)(X + row * a.ldsrc + foff[c]);
+            if constexpr (BIAS) R[c] += bv[c];
+        }
     }
     int cur = 0;
 
@@ -1870,7 +1898,10 @@ __device__ __forceinline__ void agg_fwd_split_body(const AggArgs &a, _Float16 *_
             for (int u = 0; u < U; ++u) {
                 while (cur < sj[u]) close_slot();
 #pragma unroll
-                for (int q = 0; q < CH; ++q) P[q] = vfma(wj[u], xv[u][q], P[q]);
+                for (int q = 0; q < CH; ++q) {
+                    if constexpr (BIAS) xv[u][q] += bv[q];
+                    P[q] = vfma(wj[u], xv[u][q], P[q]);
+                }
             }
         }
         for (; j < cnt; ++j) {
@@ -1882,23 +1913,40 @@ __device__ __forceinline__ void agg_fwd_split_body(const AggArgs &a, _Float16 *_
             for (int q = 0; q < CH; ++q) x1[q] = *(const f4 *)(X + (int64_t)cj * a.ldsrc + foff[q]);
             while (cur < s1) close_slot();
 #pragma unroll
-            for (int q = 0; q < CH; ++q) P[q] = vfma(w1, x1[q], P[q]);
+            for (int q = 0; q < CH; ++q) {
+                if constexpr (BIAS) x1[q] += bv[q];
+                P[q] = vfma(w1, x1[q], P[q]);
+            }
         }
     }
     while (cur < a.K) close_slot();
 }
 
-template <int LPR, int CH, int U, bool WIDE = false>
+template <int LPR, int CH, int U, bool WIDE = false, bool BIAS = false>
 __global__ __launch_bounds__(256) void agg_fwd_split_kernel(const AggArgs a, _Float16 *__restrict__ p1, _Float16 *__restrict__ p2,
                                                             float *__restrict__ scale, int32_t kp, float residual_scale)
 {
-    agg_fwd_split_body<LPR, CH, U, WIDE>(a, p1, p2, scale, kp, residual_scale, blockIdx.x);
+    agg_fwd_split_body<LPR, CH, U, WIDE, BIAS>(a, p1, p2, scale, kp, residual_scale, blockIdx.x);
 }
 // d <= 128: held to the 72 registers of seven waves per SIMD, like agg_fwd_kernel<4,32,4> (left alone the epilogue takes 74: six)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void agg_fwd_split32_kernel(
     const AggArgs a, _Float16 *__restrict__ p1, _Float16 *__restrict__ p2, float *__restrict__ scale, int32_t kp, float residual_scale)
 {
     agg_fwd_split_body<32, 1, 4>(a, p1, p2, scale, kp, residual_scale, blockIdx.x);
+}
+// the same with a gathered-row bias: a lane holds its own 4 columns of it, and three gathers in flight instead of four pay for those
+// registers.  Measured on 1 M rows with 16 M / 6 M entries (profiles/r07_agg_bias_variants.json): agg_fwd_split32_kernel on the
+// materialised rows 1.67 / 0.82 ms; four gathers in flight under the 72 registers of seven waves spill 16 bytes per lane, 1.78 / 0.91 ms;
+// four without the cap (76 registers, six waves) 1.69 / 0.86 ms; three under the cap, no spill: 1.67 / 0.82 ms
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void agg_fwd_split32_bias_kernel(
+    const AggArgs a, _Float16 *__restrict__ p1, _Float16 *__restrict__ p2, float *__restrict__ scale, int32_t kp, float residual_scale)
+{
+    agg_fwd_split_body<32, 1, 3, false, true>(a, p1, p2, scale, kp, residual_scale, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void agg_fwd_split32_u8_bias_kernel(
+    const AggArgs a, _Float16 *__restrict__ p1, _Float16 *__restrict__ p2, float *__restrict__ scale, int32_t kp, float residual_scale)
+{
+    agg_fwd_split_body<32, 1, 8, false, true>(a, p1, p2, scale, kp, residual_scale, blockIdx.x);
 }
 // small graphs (<= 200 000 rows): eight gathers in flight per lane instead of four.  A launch is then a few waves of blocks deep and its
 // time is the rows' dependent load chains, not the bandwidth: 0.242 -> 0.210 ms at 87 036 rows (1 M rows: 2.18 vs 2.21 ms, occupancy 7 -> 5)
@@ -4307,11 +4355,12 @@ int ctgcn_spmm_csr_f32(int64_t n_rows, int32_t d, const int32_t *row_ptr, const 
     return launch_agg<true>(a, v4, (hipStream_t)stream);
 }
 
-int ctgcn_core_aggregate_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr,
-                             const int32_t *col_idx, const float *val, const uint8_t *slot,
-                             const float *X, int64_t ldx, float *H, uint32_t flags,
-                             const int32_t *long_rows, int32_t n_long, int32_t long_threshold,
-                             int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes, void *stream)
+// ctgcn_core_aggregate_f32 (gather_bias null) and ctgcn_core_aggregate_bias_f32 (dense rows: ldx = d)
+static int core_aggregate_(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr,
+                           const int32_t *col_idx, const float *val, const uint8_t *slot,
+                           const float *X, int64_t ldx, const float *gather_bias, float *H, uint32_t flags,
+                           const int32_t *long_rows, int32_t n_long, int32_t long_threshold,
+                           int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes, void *stream)
 {
     if (n_rows < 0 || d <= 0 || ldx < d) return fail(CTGCN_E_INVALID, "core_aggregate: bad sizes n=%lld d=%d ldx=%lld", (long long)n_rows, d, (long long)ldx);
     if (K < 1 || K > CTGCN_MAX_SLOTS) return fail(CTGCN_E_INVALID, "core_aggregate: K=%d outside [1,%d]", K, CTGCN_MAX_SLOTS);
@@ -4323,11 +4372,32 @@ int ctgcn_core_aggregate_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t
     a.row_ptr = row_ptr; a.col = col_idx; a.val = val; a.slot = slot;
     a.src = X; a.ldsrc = ldx; a.self = nullptr; a.out = H; a.out_ld = (int64_t)K * d;
     a.flags = flags; a.accumulate = 0;
+    a.gather_bias = gather_bias;
     a.long_rows = long_rows; a.n_long = n_long; a.long_thresh = long_threshold;
     if (n_long > 0 && long_threshold < 1) return fail(CTGCN_E_INVALID, "core_aggregate: long_threshold must be >= 1");
     if (int rc = set_hub_pieces(a, K, hub_split, hub_workspace, hub_workspace_bytes, "core_aggregate")) return rc;
-    const bool v4 = (d % 4 == 0) && (ldx % 4 == 0) && ctgcn_aligned16(X) && ctgcn_aligned16(H);
+    const bool v4 = (d % 4 == 0) && (ldx % 4 == 0) && ctgcn_aligned16(X) && ctgcn_aligned16(H) && (!gather_bias || ctgcn_aligned16(gather_bias));
     return launch_agg<true>(a, v4, (hipStream_t)stream);
+}
+
+int ctgcn_core_aggregate_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr,
+                             const int32_t *col_idx, const float *val, const uint8_t *slot,
+                             const float *X, int64_t ldx, float *H, uint32_t flags,
+                             const int32_t *long_rows, int32_t n_long, int32_t long_threshold,
+                             int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes, void *stream)
+{
+    return core_aggregate_(n_rows, d, K, row_ptr, col_idx, val, slot, X, ldx, nullptr, H, flags, long_rows, n_long, long_threshold,
+                           hub_split, hub_workspace, hub_workspace_bytes, stream);
+}
+
+int ctgcn_core_aggregate_bias_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr,
+                                  const int32_t *col_idx, const float *val, const uint8_t *slot,
+                                  const float *Wt, const float *gather_bias, float *H, uint32_t flags,
+                                  const int32_t *long_rows, int32_t n_long, int32_t long_threshold,
+                                  int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes, void *stream)
+{
+    return core_aggregate_(n_rows, d, K, row_ptr, col_idx, val, slot, Wt, d, gather_bias, H, flags, long_rows, n_long, long_threshold,
+                           hub_split, hub_workspace, hub_workspace_bytes, stream);
 }
 
 size_t ctgcn_core_aggregate_split_workspace_bytes(int64_t n_rows, int32_t d, int32_t K, int32_t n_out, int32_t n_long)
@@ -4337,13 +4407,14 @@ size_t ctgcn_core_aggregate_split_workspace_bytes(int64_t n_rows, int32_t d, int
     return ctgcn_linear_workspace_bytes((n_rows + 63) / 64 * 64 * K, n_out, d) + ((size_t)n_long * K * d * 4 + 255) / 256 * 256;
 }
 
-int ctgcn_core_aggregate_split_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr, const int32_t *col_idx,
-                                   const float *val, const uint8_t *slot, const float *X, int64_t ldx, uint32_t flags,
-                                   const int32_t *long_rows, int32_t n_long, int32_t long_threshold, int32_t n_out,
-                                   const int32_t *row_order, const uint32_t *tile_mask, const int32_t *tile_base, int64_t operand_rows,
-                                   const int32_t *hub_row_dest,
-                                   int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes,
-                                   void *workspace, size_t workspace_bytes, void *stream)
+// ctgcn_core_aggregate_split_f32 (gather_bias null) and ctgcn_core_aggregate_split_bias_f32 (dense rows: ldx = d)
+static int core_aggregate_split_(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr, const int32_t *col_idx,
+                                 const float *val, const uint8_t *slot, const float *X, int64_t ldx, const float *gather_bias,
+                                 uint32_t flags, const int32_t *long_rows, int32_t n_long, int32_t long_threshold, int32_t n_out,
+                                 const int32_t *row_order, const uint32_t *tile_mask, const int32_t *tile_base, int64_t operand_rows,
+                                 const int32_t *hub_row_dest,
+                                 int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes,
+                                 void *workspace, size_t workspace_bytes, void *stream)
 {
     if (n_rows < 0 || d <= 0 || ldx < d || n_out < 1) return fail(CTGCN_E_INVALID, "core_aggregate_split: bad sizes n=%lld d=%d ldx=%lld", (long long)n_rows, d, (long long)ldx);
     if (K < 1 || K > CTGCN_MAX_SLOTS) return fail(CTGCN_E_INVALID, "core_aggregate_split: K=%d outside [1,%d]", K, CTGCN_MAX_SLOTS);
@@ -4352,6 +4423,7 @@ int ctgcn_core_aggregate_split_f32(int64_t n_rows, int32_t d, int32_t K, const i
     if (!slot && K != 1) return fail(CTGCN_E_INVALID, "core_aggregate_split: slot tags required when K > 1");
     if ((d & 3) || d > 512 || (ldx & 3) || !ctgcn_aligned16(X) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
         return fail(CTGCN_E_UNSUPPORTED, "core_aggregate_split: needs d %% 4 == 0, d <= 512, 16-byte aligned rows, 256-byte aligned workspace");
+    if (gather_bias && !ctgcn_aligned16(gather_bias)) return fail(CTGCN_E_UNSUPPORTED, "core_aggregate_split: gather_bias must be 16-byte aligned");
     if (n_long < 0 || (n_long > 0 && (!long_rows || long_threshold < 1))) return fail(CTGCN_E_INVALID, "core_aggregate_split: bad hub row list");
     if ((row_order == nullptr) != (tile_mask == nullptr)) return fail(CTGCN_E_INVALID, "core_aggregate_split: row_order and tile_mask come together");
     if (row_order && K > 64) return fail(CTGCN_E_UNSUPPORTED, "core_aggregate_split: a row plan needs K <= 64");
@@ -4376,6 +4448,7 @@ int ctgcn_core_aggregate_split_f32(int64_t n_rows, int32_t d, int32_t K, const i
     a.flags = flags; a.accumulate = 0;
     a.long_rows = long_rows; a.n_long = n_long; a.long_thresh = long_threshold;
     a.order = row_order; a.tmask = tile_mask; a.tbase = tile_base; a.tile_shift = tile_base ? 6 : 4;
+    a.gather_bias = gather_bias;
     const AggPlan p = plan_for(d, true);
     a.chunks = p.chunks;
     a.passes = p.passes;
@@ -4389,6 +4462,19 @@ int ctgcn_core_aggregate_split_f32(int64_t n_rows, int32_t d, int32_t K, const i
     const float rsc = 1.f;
     static const int force_u8 = [] { const char *e = getenv("CTGCN_AGG_U8"); return e ? atoi(e) : -1; }();      // A/B: 1 = always eight gathers in flight, 0 = never
     const bool u8 = force_u8 >= 0 ? force_u8 != 0 : n_rows <= 200000;
+#define SPLIT_LAUNCH(kernel) hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, p1, p2, scale, kp, rsc)
+    if (gather_bias) {                // the same choice of kernel as below, BIAS instantiations
+        if (row_order && K > 32) {
+            if (p.chunks <= 32) SPLIT_LAUNCH((agg_fwd_split_kernel<32, 1, 8, true, true>));
+            else if (p.chunks <= 64) SPLIT_LAUNCH((agg_fwd_split_kernel<64, 1, 8, true, true>));
+            else SPLIT_LAUNCH((agg_fwd_split_kernel<64, 2, 8, true, true>));
+        } else if (p.chunks <= 32 && u8) SPLIT_LAUNCH(agg_fwd_split32_u8_bias_kernel);
+        else if (p.chunks <= 32) SPLIT_LAUNCH(agg_fwd_split32_bias_kernel);
+        else if (p.chunks <= 64) SPLIT_LAUNCH((agg_fwd_split_kernel<64, 1, 4, false, true>));
+        else if (n_rows <= 200000) SPLIT_LAUNCH((agg_fwd_split_kernel<64, 2, 8, false, true>));
+        else SPLIT_LAUNCH((agg_fwd_split_kernel<64, 2, 4, false, true>));
+    } else
+#undef SPLIT_LAUNCH
     if (row_order && K > 32) {        // a row plan over 33-64 slots (two mask words per tile): lists this deep belong to graphs of ~1 000 nodes
         if (p.chunks <= 32) hipLaunchKernelGGL((agg_fwd_split_kernel<32, 1, 8, true>), dim3((unsigned)blocks), dim3(256), 0, st, a, p1, p2, scale, kp, rsc);
         else if (p.chunks <= 64) hipLaunchKernelGGL((agg_fwd_split_kernel<64, 1, 8, true>), dim3((unsigned)blocks), dim3(256), 0, st, a, p1, p2, scale, kp, rsc);
@@ -4410,19 +4496,46 @@ int ctgcn_core_aggregate_split_f32(int64_t n_rows, int32_t d, int32_t K, const i
         const size_t lds = per_group * G;
 #define HUBCASE(L)                                                                                                                        \
         if (p.lpr == L) {                                                                                                                 \
-            auto k = agg_fwd_hub_kernel<4, L, 4>;                                                                                        \
+            auto k = gather_bias ? agg_fwd_hub_kernel<4, L, 4, true> : agg_fwd_hub_kernel<4, L, 4>;                                       \
             if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
             hipLaunchKernelGGL(k, dim3((unsigned)a.n_long * (unsigned)(a.hub_part ? a.hub_split : 1)), dim3(HUB_THREADS), lds, st, a);    \
         }
         HUBCASE(8) else HUBCASE(16) else HUBCASE(32) else HUBCASE(64)
 #undef HUBCASE
-        if (a.hub_part) hipLaunchKernelGGL((agg_hub_final_kernel<4, true>), dim3((unsigned)a.n_long), dim3(256), 0, st, a);
+        if (a.hub_part && gather_bias) hipLaunchKernelGGL((agg_hub_final_kernel<4, true, true>), dim3((unsigned)a.n_long), dim3(256), 0, st, a);
+        else if (a.hub_part) hipLaunchKernelGGL((agg_hub_final_kernel<4, true>), dim3((unsigned)a.n_long), dim3(256), 0, st, a);
         HIP_TRY(hipGetLastError());
         const int rc = row_order ? ctgcn_split_rows_mapped_((int64_t)a.n_long * K, d, kp, hub, d, p1, p2, scale, hub_row_dest, -1, rsc, stream)
                                  : ctgcn_split_rows_mapped_((int64_t)a.n_long * K, d, kp, hub, d, p1, p2, scale, long_rows, K, rsc, stream);
         if (rc != CTGCN_OK) return rc;
     }
     return CTGCN_OK;
+}
+
+int ctgcn_core_aggregate_split_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr, const int32_t *col_idx,
+                                   const float *val, const uint8_t *slot, const float *X, int64_t ldx, uint32_t flags,
+                                   const int32_t *long_rows, int32_t n_long, int32_t long_threshold, int32_t n_out,
+                                   const int32_t *row_order, const uint32_t *tile_mask, const int32_t *tile_base, int64_t operand_rows,
+                                   const int32_t *hub_row_dest,
+                                   int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes,
+                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    return core_aggregate_split_(n_rows, d, K, row_ptr, col_idx, val, slot, X, ldx, nullptr, flags, long_rows, n_long, long_threshold, n_out,
+                                 row_order, tile_mask, tile_base, operand_rows, hub_row_dest, hub_split, hub_workspace,
+                                 hub_workspace_bytes, workspace, workspace_bytes, stream);
+}
+
+int ctgcn_core_aggregate_split_bias_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr, const int32_t *col_idx,
+                                        const float *val, const uint8_t *slot, const float *Wt, const float *gather_bias, uint32_t flags,
+                                        const int32_t *long_rows, int32_t n_long, int32_t long_threshold, int32_t n_out,
+                                        const int32_t *row_order, const uint32_t *tile_mask, const int32_t *tile_base, int64_t operand_rows,
+                                        const int32_t *hub_row_dest,
+                                        int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes,
+                                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    return core_aggregate_split_(n_rows, d, K, row_ptr, col_idx, val, slot, Wt, d, gather_bias, flags, long_rows, n_long, long_threshold, n_out,
+                                 row_order, tile_mask, tile_base, operand_rows, hub_row_dest, hub_split, hub_workspace,
+                                 hub_workspace_bytes, workspace, workspace_bytes, stream);
 }
 
 int ctgcn_core_aggregate_bwd_prep_f32(int64_t n_rows, int32_t d, int32_t K, const float *dH,

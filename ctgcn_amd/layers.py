@@ -193,22 +193,26 @@ class CoreDiffusion(nn.Module):
         self.rnn = _RNN[rnn_type](input_size=input_dim, hidden_size=output_dim, num_layers=1, bias=bias, batch_first=True)
         self.norm = nn.LayerNorm(output_dim)
 
-    def aggregate(self, x, adj_list):
+    def aggregate(self, x, adj_list, gather_bias=None):
         """[N, K, input_dim] = all K rectified cumulative aggregations, one kernel launch."""
-        return ops.core_aggregate(x, as_core_adj(adj_list, x.device), relu=True)
+        if gather_bias is None:
+            return ops.core_aggregate(x, as_core_adj(adj_list, x.device), relu=True)
+        return ops.core_aggregate(x, as_core_adj(adj_list, x.device), relu=True, gather_bias=gather_bias)
 
-    def forward(self, x, adj_list, out=None):
-        """out (optional, inference): a [N, output_dim] view (unit column stride) that receives the result."""
+    def forward(self, x, adj_list, out=None, gather_bias=None):
+        """out (optional, inference): a [N, output_dim] view (unit column stride) that receives the result.
+        gather_bias (optional, [input_dim]): x is the first Linear's weight stored by input row (ops.to_gather_layout) and the layer's
+        input is x + gather_bias = Linear(one-hot features), which the aggregation kernels form row by row in registers."""
         if torch.is_tensor(x) and not x.is_sparse and x.is_cuda:
             adj = as_core_adj(adj_list, x.device)
             if ops.aggregate_split_ok(self.rnn, x, adj):
                 # inference, GRU input projection on the split GEMM (d_in != 128): the aggregation writes the GEMM's fp16 operand
                 # planes, the fp32 [N, K, input_dim] tensor is never materialised
-                return ops.core_diffusion_split(x, adj, self.rnn, self.norm, out=out)
+                return ops.core_diffusion_split(x, adj, self.rnn, self.norm, out=out, gather_bias=gather_bias)
             if torch.is_grad_enabled() and ops.core_diffusion_fused_ok(self.rnn, self.norm, x, adj):
                 # training, d_in = hidden = 128: the inference forward under autograd (planes + row plan kept for the backward kernels)
-                return ops.core_diffusion_fused(x, adj, self.rnn, self.norm)
-        seq = self.aggregate(x, adj_list)            # [batch = N, seq = K, feat]
+                return ops.core_diffusion_fused(x, adj, self.rnn, self.norm, gather_bias=gather_bias)
+        seq = self.aggregate(x, adj_list, gather_bias)            # [batch = N, seq = K, feat]
         return rnn_reduce_norm(self.rnn, self.norm, seq, reduce_sum=True, out=out)
 
 
@@ -245,14 +249,16 @@ class MLP(nn.Module):
             out = torch.sparse.mm(h, layer.weight.t())
             return (out if layer.bias is None else out + layer.bias), False
         needs_grad = torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in layer.parameters()))
-        if not needs_grad and h.dim() == 2 and ops.linear_split_ok(h, layer.weight):
+        # a weight that one-hot forwards re-laid by input row (ops.to_gather_layout) meets dense features: a row-major copy, same products
+        weight = layer.weight.contiguous() if ops.in_gather_layout(layer.weight) else layer.weight
+        if not needs_grad and h.dim() == 2 and ops.linear_split_ok(h, weight):
             # fp32-accurate split GEMM on the 16-bit matrix cores (inference), SELU in its epilogue
-            return ops.linear_split(h, layer.weight, layer.bias, selu=selu, static_x=static_x), bool(selu)
-        if needs_grad and h.dim() == 2 and ops.linear_train_enabled() and ops.linear_split_ok(h, layer.weight) and ops.plane_cache_enabled() \
+            return ops.linear_split(h, weight, layer.bias, selu=selu, static_x=static_x), bool(selu)
+        if needs_grad and h.dim() == 2 and ops.linear_train_enabled() and ops.linear_split_ok(h, weight) and ops.plane_cache_enabled() \
                 and h.shape[0] >= 4096:
             # training: forward and dx on the same GEMM (ops._LinearSplit); small inputs stay with the library (launch-bound either way)
-            return ops.linear_split_train(h, layer.weight, layer.bias, static_x=static_x), False
-        return layer(h), False
+            return ops.linear_split_train(h, weight, layer.bias, static_x=static_x), False
+        return (layer(h) if weight is layer.weight else F.linear(h, weight, layer.bias)), False
 
     def forward(self, x):
         stack = [self.linear] if self.layer_num == 1 else list(self.linears)

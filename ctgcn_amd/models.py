@@ -34,11 +34,12 @@ class CDN(nn.Module):
         self.diffusion_list = nn.ModuleList(
             CoreDiffusion(a, b, bias=bias, rnn_type=rnn_type) for a, b in zip(dims[:-1], dims[1:]))
 
-    def forward(self, x, adj_list, out=None):
-        """out (optional, inference): where the LAST layer writes its [N, output_dim] result (see CoreDiffusion.forward)."""
+    def forward(self, x, adj_list, out=None, gather_bias=None):
+        """out (optional, inference): where the LAST layer writes its [N, output_dim] result; gather_bias (optional): the FIRST layer's
+        input is x + gather_bias, formed inside its aggregation (see CoreDiffusion.forward)."""
         last = len(self.diffusion_list) - 1
         for i, layer in enumerate(self.diffusion_list):
-            x = layer(x, adj_list, out=out if i == last else None)
+            x = layer(x, adj_list, out=out if i == last else None, gather_bias=gather_bias if i == 0 else None)
         return x
 
 
@@ -132,8 +133,34 @@ class CTGCN(nn.Module):
         self.norm = nn.LayerNorm(output_dim)
         self.process_group = None      # set by snapshot_parallel.shard_ctgcn()
 
+    def gather_operand(self, t, x):
+        """(Wt [N, width], bias or None) when snapshot t's MLP output Linear(one-hot x) = W^T + b need not exist: CTGCN-C (nobody but the
+        first CoreDiffusion layer reads it), one Linear without activation, identity features on the weight's device.  The aggregation then
+        gathers rows of the weight itself and adds the bias in registers (ops.core_aggregate(..., gather_bias)), for which the weight is
+        stored by input row from its first such forward on (ops.to_gather_layout: one copy, in place).  None: the MLP runs as usual
+        (CTGCN_LINEAR_GATHER=0 forces that)."""
+        from .layers import _is_identity
+        mlp = self.mlp_list[t]
+        if self.model_type != 'C' or mlp.layer_num != 1 or mlp.activate_type != 'L' or not ops.linear_gather_enabled():
+            return None
+        w, b = mlp.linear.weight, mlp.linear.bias
+        if not (torch.is_tensor(x) and x.is_sparse and x.is_cuda and w.device == x.device and w.dtype == torch.float32
+                and x.shape[1] == w.shape[1] and _is_identity(x)):
+            return None
+        if b is not None and (b.dtype != torch.float32 or not b.is_contiguous() or b.data_ptr() % 16):
+            return None
+        if not w.t().is_contiguous():
+            if torch.cuda.is_current_stream_capturing():
+                return None                      # no re-layout inside a capture (the warm-up forwards of GraphedInference have done it)
+            ops.to_gather_layout(w)
+        return w.t(), b
+
     def snapshot_branch(self, t, x, adj, out=None):
-        """Everything that is independent per snapshot: reference models.py:244-246."""
+        """Everything that is independent per snapshot: reference models.py:244-246.  Returns (embeddings, MLP output); the MLP output
+        is None where it was never formed (gather_operand)."""
+        g = self.gather_operand(t, x)
+        if g is not None:
+            return self.duffision_list[t](g[0], adj, out=out, gather_bias=g[1]), None
         trans = self.mlp_list[t](x)
         return self.duffision_list[t](trans, adj, out=out), trans
 
@@ -342,10 +369,13 @@ class CTGCN(nn.Module):
         elif g0 is not None:
             # small window: the MLP and the layers before g0 per snapshot (on the lanes), then the width-128 layers of ALL snapshots per launch
             def head(t):
-                tr = self.mlp_list[t](x_list[t])
-                h = tr
+                # (a first layer in front of the grouped ones can gather the MLP's weight rows itself: gather_operand; with g0 = 0 the
+                # grouped launch reads a materialised MLP output)
+                g = self.gather_operand(t, x_list[t]) if g0 >= 1 else None
+                tr = self.mlp_list[t](x_list[t]) if g is None else None
+                h = tr if g is None else g[0]
                 for l in range(g0):
-                    h = self.duffision_list[t].diffusion_list[l](h, adj_list[t])
+                    h = self.duffision_list[t].diffusion_list[l](h, adj_list[t], gather_bias=g[1] if (g is not None and l == 0) else None)
                 return h, tr
             if lanes:
                 main = torch.cuda.current_stream(seq.device)
@@ -355,7 +385,8 @@ class CTGCN(nn.Module):
                     with torch.cuda.stream(lanes[t % len(lanes)]):
                         h, tr = head(t)
                         h.record_stream(main)
-                        tr.record_stream(main)
+                        if tr is not None:
+                            tr.record_stream(main)
                     hx.append(h)
                     trans.append(tr)
                 for s_ in lanes:
@@ -377,7 +408,8 @@ class CTGCN(nn.Module):
                     h, tr = self.snapshot_branch(t, x_list[t], adj_list[t], out=seq[:, t])
                     if h.data_ptr() != seq[:, t].data_ptr():
                         seq[:, t].copy_(h)
-                    tr.record_stream(main)                 # returned to the caller ('S'), who uses it on the main stream
+                    if tr is not None:
+                        tr.record_stream(main)             # returned to the caller ('S'), who uses it on the main stream
                 hx.append(h)
                 trans.append(tr)
             for s_ in lanes:
@@ -393,7 +425,8 @@ class CTGCN(nn.Module):
                 with torch.cuda.stream(tl[t % len(tl)]):
                     h, tr = self.snapshot_branch(t, x_list[t], adj_list[t])
                     h.record_stream(main)
-                    tr.record_stream(main)
+                    if tr is not None:
+                        tr.record_stream(main)
                 hx.append(h)
                 trans.append(tr)
             for s_ in tl:

@@ -147,10 +147,36 @@ def spmm_csr(row_ptr, col, val, x, out=None, accumulate=False):
     return out
 
 
+def linear_gather_enabled():
+    """CTGCN_LINEAR_GATHER=0: the first CoreDiffusion layer of a one-hot CTGCN-C branch reads a materialised Linear(I) = W^T + b
+    (ctgcn_transpose_bias_f32 per snapshot and forward) instead of gathering the weight's rows and adding the bias in registers, and the
+    weight keeps its [out, N] row-major memory — for A/B runs."""
+    import os
+    return os.environ.get("CTGCN_LINEAR_GATHER", "1") != "0"
+
+
+def in_gather_layout(weight):
+    """True when weight [out, N] is stored by input row: weight.t() is a contiguous [N, out] buffer (strides (1, out))."""
+    return weight.dim() == 2 and weight.stride(1) != 1 and weight.t().is_contiguous()
+
+
+def to_gather_layout(weight):
+    """Re-lay the parameter weight [out, N] in place as the .t() view of a contiguous [N, out] buffer (one copy, once): same shape, same
+    values, same state_dict entry; row v of the buffer is what Linear makes of one-hot node v before the bias.  load_state_dict
+    (copy_ into the parameter), deepcopy and .to() (preserve_format) keep the layout; the optimizer's per-element updates do not see it."""
+    if weight.dim() != 2 or weight.t().is_contiguous():
+        return weight
+    with torch.no_grad():
+        weight.data = weight.detach().t().contiguous().t()
+    return weight
+
+
 def _transpose_bias(src, bias):
     """out[n, d] = src[d, n]^T + bias[d] (bias may be None), row-major, one pass (ctgcn_transpose_bias_f32)"""
     lib = _lib.load()
     d, n = src.shape
+    if in_gather_layout(src):          # stored by input row already (to_gather_layout): the same fp32 add per element, no transpose
+        return src.t() + bias if bias is not None else src.t().clone()
     w = src if src.stride(1) == 1 else src.contiguous()
     out = torch.empty(n, d, dtype=torch.float32, device=src.device)
     with torch.cuda.device(src.device):
@@ -196,7 +222,16 @@ def _hub_pieces(lib, adj, long_rows, slots, d, device, transposed=False):
     return split, torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
 
 
-def _aggregate_fwd(adj, x, relu):
+def _check_gather_bias(x, gather_bias):
+    """the operand of the *_bias_f32 entry points: x [n, d] dense rows (a Linear weight stored by input row), gather_bias fp32 [d]"""
+    if not x.is_contiguous():
+        raise ValueError("gather_bias goes with dense [n, d] rows (a weight in gather layout), got strides %s" % (tuple(x.stride()),))
+    if gather_bias.dtype != torch.float32 or gather_bias.shape != (x.shape[1],) or gather_bias.device != x.device or not gather_bias.is_contiguous():
+        raise ValueError("gather_bias must be a contiguous fp32 [%d] vector on %s" % (x.shape[1], x.device))
+
+
+def _aggregate_fwd(adj, x, relu, gather_bias=None):
+    """gather_bias [d] (optional): the operand rows are x[row] + gather_bias, added in registers (ctgcn_core_aggregate_bias_f32)"""
     lib = _lib.load()
     n, d = x.shape
     H = torch.empty(n, adj.K, d, dtype=torch.float32, device=x.device)
@@ -204,6 +239,12 @@ def _aggregate_fwd(adj, x, relu):
     with torch.cuda.device(x.device), _timed("agg_fwd", n=n, d=d, K=adj.K, nnz=adj.nnz):
         long_rows = adj.long_rows()
         split, hub_ws, hub_bytes = _hub_pieces(lib, adj, long_rows, adj.K, d, x.device)
+        if gather_bias is not None:
+            _check_gather_bias(x, gather_bias)
+            check(lib.ctgcn_core_aggregate_bias_f32(n, d, adj.K, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(adj.slot), ptr(x),
+                                                    ptr(gather_bias), ptr(H), flags, ptr(long_rows), 0 if long_rows is None else long_rows.numel(),
+                                                    adj.LONG_ROW, split, ptr(hub_ws), hub_bytes, _stream()), "ctgcn_core_aggregate_bias_f32")
+            return H
         check(lib.ctgcn_core_aggregate_f32(n, d, adj.K, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(adj.slot), ptr(x),
                                            x.stride(0), ptr(H), flags, ptr(long_rows), 0 if long_rows is None else long_rows.numel(),
                                            adj.LONG_ROW, split, ptr(hub_ws), hub_bytes, _stream()), "ctgcn_core_aggregate_f32")
@@ -240,8 +281,8 @@ def _aggregate_bwd(adj, H, dH, relu):
 
 class _CoreAggregate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, adj, relu):
-        H = _aggregate_fwd(adj, x, relu)
+    def forward(ctx, x, adj, relu, gather_bias):
+        H = _aggregate_fwd(adj, x, relu, None if gather_bias is None else gather_bias.detach())
         ctx.adj, ctx.relu = adj, relu
         ctx.save_for_backward(H)
         return H
@@ -250,11 +291,16 @@ class _CoreAggregate(torch.autograd.Function):
     def backward(ctx, dH):
         (H,) = ctx.saved_tensors
         dH = dH.contiguous()
-        return _aggregate_bwd(ctx.adj, H, dH, ctx.relu), None, None
+        dX = _aggregate_bwd(ctx.adj, H, dH, ctx.relu)
+        # every operand row is x[row] + gather_bias: dX is the gradient of that sum, the bias takes its column sum (what
+        # _LinearOfIdentity.backward makes of the same dX)
+        return dX, None, None, (dX.sum(0) if ctx.needs_input_grad[3] else None)
 
 
-def core_aggregate(x, adj, relu=True):
-    """H[N, K, d] with H[:, j, :] = relu(sum_{i<=j} A_i x)  — layers.py:41-48 and the layout of :58."""
+def core_aggregate(x, adj, relu=True, gather_bias=None):
+    """H[N, K, d] with H[:, j, :] = relu(sum_{i<=j} A_i x)  — layers.py:41-48 and the layout of :58.
+    gather_bias [d] (optional): x is a Linear weight stored by input row and the aggregated operand is x + gather_bias, never
+    materialised (see _aggregate_fwd); differentiable in both."""
     _need_cuda(x, adj.col)
     if adj.K < 1:
         raise ValueError("empty k-core adjacency list")
@@ -265,7 +311,7 @@ def core_aggregate(x, adj, relu=True):
     if x.device != adj.device:
         raise ValueError("features on %s but adjacency on %s" % (x.device, adj.device))
     x = x if x.stride(1) == 1 else x.contiguous()
-    return _CoreAggregate.apply(x, adj, relu)
+    return _CoreAggregate.apply(x, adj, relu, gather_bias)
 
 
 # ------------------------------------------------------------- GRU over the core / time axis (+ sum, LayerNorm)
@@ -817,10 +863,11 @@ def row_plan_enabled():
     return os.environ.get("CTGCN_DEDUP", "1") != "0"
 
 
-def aggregate_split_planes(x, adj, n_out, plan=None, ws=None):
+def aggregate_split_planes(x, adj, n_out, plan=None, ws=None, gather_bias=None):
     """ctgcn_core_aggregate_split_f32: relu(cumulative A_k x) as fp16 planes + row scales in a workspace (returned).  n_out = width of
     the GEMM that follows (1: the GRU layer kernel).  plan = adj.row_plan(tile): repeated rows are not written — tile 16 with the layer
-    kernel as consumer (holes in the [n K] row layout), tile 64 with the GEMM (compact operand rows, plan["operand_rows"] of them)."""
+    kernel as consumer (holes in the [n K] row layout), tile 64 with the GEMM (compact operand rows, plan["operand_rows"] of them).
+    gather_bias [d] (optional): operand rows x[row] + gather_bias, x dense (ctgcn_core_aggregate_split_bias_f32)."""
     lib = _lib.load()
     n, d = x.shape
     flags = adj.flags | _lib.F_RELU
@@ -835,6 +882,15 @@ def aggregate_split_planes(x, adj, n_out, plan=None, ws=None):
     hub_dest = adj.plan_row_dest(plan, long_rows, compact) if (plan is not None and n_long) else None
     split, hub_ws, hub_bytes = _hub_pieces(lib, adj, long_rows, adj.K, d, x.device)
     with _timed("agg_fwd", n=n, d=d, K=adj.K, nnz=adj.nnz, split=True, rows_written=(plan["new_rows"] if plan is not None else n * adj.K)):
+        if gather_bias is not None:
+            _check_gather_bias(x, gather_bias)
+            check(lib.ctgcn_core_aggregate_split_bias_f32(n, d, adj.K, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(adj.slot), ptr(x), ptr(gather_bias),
+                                                          flags, ptr(long_rows), n_long, adj.LONG_ROW, n_out,
+                                                          ptr(plan["order"]) if plan is not None else None, ptr(plan["tile_mask"]) if plan is not None else None,
+                                                          ptr(plan["tile_base"]) if compact else None, plan["operand_rows"] if compact else 0,
+                                                          ptr(hub_dest), split, ptr(hub_ws), hub_bytes, ptr(ws), ws_bytes, _stream()),
+                  "ctgcn_core_aggregate_split_bias_f32")
+            return ws, ws_bytes
         check(lib.ctgcn_core_aggregate_split_f32(n, d, adj.K, ptr(adj.row_ptr), ptr(adj.col), ptr(adj.val), ptr(adj.slot), ptr(x), x.stride(0),
                                                  flags, ptr(long_rows), n_long, adj.LONG_ROW, n_out,
                                                  ptr(plan["order"]) if plan is not None else None, ptr(plan["tile_mask"]) if plan is not None else None,
@@ -859,11 +915,12 @@ def gru_layer_presplit(ws, n, K, rnn, norm, out, plan=None):
     return out
 
 
-def core_diffusion_split(x, adj, rnn, norm, out=None):
+def core_diffusion_split(x, adj, rnn, norm, out=None, gather_bias=None):
     """LayerNorm(sum_k GRU(relu(cumulative A_k x))_k) — CoreDiffusion.forward (layers.py:41-62) for inference, no fp32 H:
     aggregation -> fp16 planes + row scales, then  d_in = hidden = 128: the register-resident GRU layer kernel reads the planes
     (under the graph's row plan: rows of H that repeat the row before are neither written nor multiplied by W_ih again);
-    d_in != 128: split GEMM -> gate pre-activations -> recurrence + sum + LayerNorm kernel."""
+    d_in != 128: split GEMM -> gate pre-activations -> recurrence + sum + LayerNorm kernel.
+    gather_bias: see aggregate_split_planes."""
     lib = _lib.load()
     n, d = x.shape
     K, hid = adj.K, rnn.hidden_size
@@ -876,7 +933,7 @@ def core_diffusion_split(x, adj, rnn, norm, out=None):
     with torch.cuda.device(x.device):
         if d == hid:                                       # -> ctgcn_gru_layer_presplit_f32; its weights need no plane workspace
             plan = adj.row_plan() if row_plan_enabled() else None
-            ws, _ = aggregate_split_planes(x, adj, 1, plan)
+            ws, _ = aggregate_split_planes(x, adj, 1, plan, gather_bias=gather_bias)
             return gru_layer_presplit(ws, n, K, rnn, norm, out, plan)
         bias, b_hn = _gru_bias(rnn, hid)
         w_ih, w_hh = rnn.weight_ih_l0.detach(), rnn.weight_hh_l0.detach().contiguous()
@@ -885,7 +942,7 @@ def core_diffusion_split(x, adj, rnn, norm, out=None):
         eps = 0.0 if norm is None else float(norm.eps)
         plan = adj.row_plan(adj.PLAN_TILE_GEMM) if (row_plan_enabled() and forward_split_mode() == 2) else None
         rows = plan["operand_rows"] if plan is not None else n * K          # under a plan the GEMM only sees rows that bring a new x
-        ws, ws_bytes = aggregate_split_planes(x, adj, n_out, plan)
+        ws, ws_bytes = aggregate_split_planes(x, adj, n_out, plan, gather_bias=gather_bias)
         gi_buf = torch.empty(rows * n_out, dtype=torch.float32, device=x.device) if plan is not None else _gi_buffer(n, K, hid, x.device)
         with _timed("linear_split", rows=rows, k=d, n_out=n_out, presplit=True):
             if plane_cache_enabled():          # W_ih's packed operand: built once per weight version, not per call
@@ -945,13 +1002,15 @@ class _CoreDiffusionFused(torch.autograd.Function):
                dx + dW_ih + the aggregation's mask / suffix sums (Z, S0); then ONE gather (ctgcn_core_aggregate_bwd_f32)."""
 
     @staticmethod
-    def forward(ctx, x, adj, w_ih, w_hh, b_ih, b_hh, ln_w, ln_b, eps):
+    def forward(ctx, x, adj, w_ih, w_hh, b_ih, b_hh, ln_w, ln_b, eps, gather_bias):
         lib = _lib.load()
         n, K, hid = adj.n, adj.K, w_hh.shape[1]
         plan = adj.row_plan() if row_plan_enabled() else None
         x_d = x.detach()
+        gb = None if gather_bias is None else gather_bias.detach()     # operand rows x[row] + gather_bias (aggregate_split_planes)
+        ctx.gather_bias = gb
         with torch.cuda.device(x.device):
-            ws, _ = aggregate_split_planes(x_d, adj, 1, plan)
+            ws, _ = aggregate_split_planes(x_d, adj, 1, plan, gather_bias=gb)
             bias, b_hn = _fold_gru_bias(b_ih, b_hh, hid)
             out = torch.empty(n, hid, dtype=torch.float32, device=x.device)
             with _timed("gru_layer", rows=n, steps=K, reduce_sum=True, presplit=True, new_rows=(plan["new_rows"] if plan is not None else n * K)):
@@ -980,7 +1039,7 @@ class _CoreDiffusionFused(torch.autograd.Function):
         ws, w_ih, w_hh, b_ih, b_hh, ln_w, ln_b = ctx.saved_tensors
         if not ctx.kept:
             with torch.cuda.device(ws.device):
-                ws, _ = aggregate_split_planes(ws, ctx.adj, 1, ctx.plan)          # ws was the layer's input x
+                ws, _ = aggregate_split_planes(ws, ctx.adj, 1, ctx.plan, gather_bias=ctx.gather_bias)          # ws was the layer's input x
         adj, plan, eps = ctx.adj, ctx.plan, ctx.eps
         n, K, hid = adj.n, adj.K, w_hh.shape[1]
         dev = ws.device
@@ -1026,14 +1085,17 @@ class _CoreDiffusionFused(torch.autograd.Function):
                                                    ptr(Z) if order is not None else ptr(Z[lo:]),
                                                    ptr(S0) if (S0 is None or order is not None) else ptr(S0[lo:]), od, 1 if adj.nested else 0,
                                                    ptr(dw_ih_part), ptr(dbi_part), nb, 1, _stream()), "ctgcn_gru_bwd_in_f32")
-            dX = _aggregate_gather(adj, Z, S0, True) if ctx.needs_input_grad[0] else None
+            need_gb = ctx.gather_bias is not None and ctx.needs_input_grad[9]
+            dX = _aggregate_gather(adj, Z, S0, True) if (ctx.needs_input_grad[0] or need_gb) else None
         dw_ih = dw_ih_part.sum(0)
         dw_hh = dw_hh_part.sum(0)
         db_ih = db_hh = None
         if b_ih is not None:
             db_ih = dbi_part.sum(0)
             db_hh = torch.cat([db_ih[: 2 * hid], dbn_part.sum(0)])
-        return dX, None, dw_ih, dw_hh, db_ih, db_hh, ln_sum[:hid].clone(), ln_sum[hid:].clone(), None
+        # (gather_bias: dX is the gradient of x[row] + gather_bias, so the bias takes its column sum, as in _LinearOfIdentity.backward)
+        d_gb = dX.sum(0) if (ctx.gather_bias is not None and ctx.needs_input_grad[9]) else None
+        return dX, None, dw_ih, dw_hh, db_ih, db_hh, ln_sum[:hid].clone(), ln_sum[hid:].clone(), None, d_gb
 
 
 def _fold_gru_bias(b_ih, b_hh, hid):
@@ -1045,11 +1107,11 @@ def _fold_gru_bias(b_ih, b_hh, hid):
     return bias, b_hh.detach()[2 * hid:].contiguous()
 
 
-def core_diffusion_fused(x, adj, rnn, norm):
+def core_diffusion_fused(x, adj, rnn, norm, gather_bias=None):
     """CoreDiffusion.forward (layers.py:41-62) with autograd, see _CoreDiffusionFused (core_diffusion_fused_ok decides)."""
     b_ih = rnn.bias_ih_l0 if rnn.bias else None
     b_hh = rnn.bias_hh_l0 if rnn.bias else None
-    return _CoreDiffusionFused.apply(x, adj, rnn.weight_ih_l0, rnn.weight_hh_l0, b_ih, b_hh, norm.weight, norm.bias, float(norm.eps))
+    return _CoreDiffusionFused.apply(x, adj, rnn.weight_ih_l0, rnn.weight_hh_l0, b_ih, b_hh, norm.weight, norm.bias, float(norm.eps), gather_bias)
 
 
 # ------------------------------------------------------------- a window of small snapshots: one launch per kernel

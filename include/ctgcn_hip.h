@@ -107,6 +107,18 @@ int ctgcn_core_aggregate_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t
                              const float *X, int64_t ldx, float *H, uint32_t flags,
                              const int32_t *long_rows, int32_t n_long, int32_t long_threshold,
                              int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes, void *stream);
+/*
+ * The same aggregation over the rows of Linear(one-hot features) = W^T + b (layers.py:95-106 on helper.py:161-172) without that matrix:
+ * Wt is the Linear's weight stored by input row, [n_rows, d] dense (row stride d), and every operand row the kernels read - a gathered
+ * neighbour row or the row's own self-loop row - is Wt[row] + gather_bias as ONE fp32 add in registers before the multiply-accumulate:
+ * the value a materialised W^T + b would have held, so H is bit-identical to ctgcn_core_aggregate_f32 on that matrix (hub rows and
+ * hub rows cut into pieces included).  gather_bias: float[d] or NULL (NULL: ctgcn_core_aggregate_f32 with ldx = d).
+ */
+int ctgcn_core_aggregate_bias_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr,
+                                  const int32_t *col_idx, const float *val, const uint8_t *slot,
+                                  const float *Wt, const float *gather_bias, float *H, uint32_t flags,
+                                  const int32_t *long_rows, int32_t n_long, int32_t long_threshold,
+                                  int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes, void *stream);
 
 /*
  * Backward of ctgcn_core_aggregate_f32 w.r.t. X (what autograd derives for layers.py:41-48).
@@ -475,6 +487,15 @@ int ctgcn_core_aggregate_split_f32(int64_t n_rows, int32_t d, int32_t K, const i
                                    const int32_t *hub_row_dest,
                                    int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes,
                                    void *workspace, size_t workspace_bytes, void *stream);
+/* ctgcn_core_aggregate_split_f32 with operand rows Wt[row] + gather_bias (see ctgcn_core_aggregate_bias_f32): Wt [n_rows, d] dense,
+ * gather_bias float[d], 16-byte aligned, or NULL; planes and row scales bit-identical to the call on the materialised W^T + b. */
+int ctgcn_core_aggregate_split_bias_f32(int64_t n_rows, int32_t d, int32_t K, const int32_t *row_ptr, const int32_t *col_idx,
+                                        const float *val, const uint8_t *slot, const float *Wt, const float *gather_bias, uint32_t flags,
+                                        const int32_t *long_rows, int32_t n_long, int32_t long_threshold, int32_t n_out,
+                                        const int32_t *row_order, const uint32_t *tile_mask, const int32_t *tile_base, int64_t operand_rows,
+                                        const int32_t *hub_row_dest,
+                                        int32_t hub_split, void *hub_workspace, size_t hub_workspace_bytes,
+                                        void *workspace, size_t workspace_bytes, void *stream);
 int ctgcn_linear_presplit_f32(int64_t rows, int32_t n_out, int32_t k, const float *w, int64_t ldw, const float *bias, float *y, int64_t ldy,
                               void *workspace, size_t workspace_bytes, void *stream);
 
