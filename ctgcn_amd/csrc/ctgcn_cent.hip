@@ -434,10 +434,10 @@ extern "C" size_t ctgcn_cent_eigenvector_workspace_bytes(int64_t n)
 }
 
 extern "C" int ctgcn_cent_eigenvector(int64_t n, const int32_t *row_ptr, const int32_t *col, int32_t max_iter, double tol, double *x_out,
-                                      int32_t *stop_step, void *workspace, size_t workspace_bytes, void *stream)
+                                      int32_t *stop_step_host, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (n < 1 || max_iter < 0) return ctgcn_set_error_(CTGCN_E_INVALID, "cent_eigenvector: bad sizes (need n >= 1, max_iter >= 0)");
-    if (!row_ptr || !col || !x_out || !stop_step || !workspace) return ctgcn_set_error_(CTGCN_E_INVALID, "cent_eigenvector: null pointer");
+    if (!row_ptr || !col || !x_out || !stop_step_host || !workspace) return ctgcn_set_error_(CTGCN_E_INVALID, "cent_eigenvector: null pointer");
     if (workspace_bytes < ctgcn_cent_eigenvector_workspace_bytes(n))
         return ctgcn_set_error_(CTGCN_E_WORKSPACE, "cent_eigenvector: workspace too small");
     hipStream_t st = (hipStream_t)stream;
@@ -457,7 +457,7 @@ extern "C" int ctgcn_cent_eigenvector(int64_t n, const int32_t *row_ptr, const i
     EigCtrl h{};
     CTGCN_TRY(hipMemcpyAsync(&h, ctrl, sizeof(EigCtrl), hipMemcpyDeviceToHost, st));
     CTGCN_TRY(hipStreamSynchronize(st));
-    *stop_step = h.done ? h.stop_step : 0;
+    *stop_step_host = h.done ? h.stop_step : 0;
     return CTGCN_OK;
 }
 

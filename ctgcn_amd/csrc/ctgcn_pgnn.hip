@@ -530,12 +530,12 @@ extern "C" size_t ctgcn_pgnn_dist_workspace_bytes(void) { return 16; }
 
 extern "C" int ctgcn_pgnn_anchor_dist(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *col, int32_t n_sets,
                                       const int32_t *offsets, const int32_t *members, int32_t n_members, int32_t cutoff, int32_t *level,
-                                      float *dist_max, int32_t *pos, int32_t *node_id, int32_t *levels_run, void *workspace,
+                                      float *dist_max, int32_t *pos, int32_t *node_id, int32_t *levels_run_host, void *workspace,
                                       size_t workspace_bytes, void *stream)
 {
     if (n < 0 || n >= (int64_t)1 << 31 || nnz < 0 || nnz >= (int64_t)1 << 31 || n_sets < 1 || n_members < 0)
         return ctgcn_set_error_(CTGCN_E_INVALID, "ctgcn_pgnn_anchor_dist: bad sizes (0 <= n, nnz < 2^31, n_sets >= 1, n_members >= 0)");
-    if (levels_run) *levels_run = 0;
+    if (levels_run_host) *levels_run_host = 0;
     if (n == 0) return CTGCN_OK;
     if (n * n_sets >= (int64_t)1 << 31) return ctgcn_set_error_(CTGCN_E_UNSUPPORTED, "ctgcn_pgnn_anchor_dist: n n_sets reaches 2^31");
     if (!row_ptr || (!col && nnz > 0) || !offsets || (!members && n_members > 0) || !level || !dist_max || !pos)
@@ -578,7 +578,7 @@ extern "C" int ctgcn_pgnn_anchor_dist(int64_t n, int64_t nnz, const int32_t *row
         CTGCN_TRY(hipStreamSynchronize(st));
         if (!host[0]) break;
     }
-    if (levels_run) *levels_run = L;
+    if (levels_run_host) *levels_run_host = L;
     dist_final_kernel<<<dim3(grid), dim3(256), 0, st>>>(a);
     CTGCN_TRY(hipGetLastError());
     return CTGCN_OK;

@@ -695,7 +695,7 @@ int ctgcn_lp_scores_f32(int64_t n, int32_t d, int32_t models, uint32_t measures,
  *   unless one slab is larger).
  * ctgcn_cent_eigenvector: networkx's eigenvector_centrality iteration: x = 1/n, then up to max_iter steps x <- (A+I)x / ||(A+I)x||_2
  *   (a zero norm counts as 1), stopping after the first step with Σ|x - x_last| < n·tol.  All steps are enqueued at once; after the
- *   stop test passes a device flag turns the rest into no-ops.  x_out (double[n]) holds x; *stop_step (host) = the stop step
+ *   stop test passes a device flag turns the rest into no-ops.  x_out (double[n]) holds x; *stop_step_host = the stop step
  *   (1-based), or 0 when no step passed the test.  One host read: the call synchronises `stream`.
  *   workspace: ctgcn_cent_eigenvector_workspace_bytes.
  * ctgcn_ridge_gram_{f32,f64}: the k-fold (KFold(folds), unshuffled: contiguous folds, the first n % folds one row longer) augmented
@@ -710,7 +710,7 @@ int ctgcn_cent_brandes(int64_t n, const int32_t *row_ptr, const int32_t *col, in
                        int64_t *r_out, int64_t *D_out, void *workspace, size_t workspace_bytes, void *stream);
 size_t ctgcn_cent_eigenvector_workspace_bytes(int64_t n);
 int ctgcn_cent_eigenvector(int64_t n, const int32_t *row_ptr, const int32_t *col, int32_t max_iter, double tol, double *x_out,
-                           int32_t *stop_step, void *workspace, size_t workspace_bytes, void *stream);
+                           int32_t *stop_step_host, void *workspace, size_t workspace_bytes, void *stream);
 size_t ctgcn_ridge_gram_workspace_bytes(int32_t d, int32_t targets, int32_t folds);
 int ctgcn_ridge_gram_f32(int64_t n, int32_t d, int32_t targets, int32_t folds, const float *X, int64_t ldx, const double *Y,
                          double *gram_out, void *workspace, size_t workspace_bytes, void *stream);
@@ -1121,7 +1121,7 @@ int ctgcn_bn_bwd_f32(int64_t n, int32_t d, const float *x, int64_t ldx, const fl
  *   fastest: level (hops to the closest anchor of the set, -1 unreached; int32, so no distance wraps), dist_max = 1 / (level + 1) as
  *   fp32 division (0 unreached), pos = the position inside the set of the closest anchor, the smallest among equally close ones (0
  *   unreached): the reference's np.max / np.argmax over its dense matrix; node_id, when not null, members[offsets[s] + pos] (0 for an
- *   empty set).  levels_run (host, may be null) receives the number of passes.  The only atomic is an integer minimum while seeding;
+ *   empty set).  levels_run_host (may be null) receives the number of passes.  The only atomic is an integer minimum while seeding;
  *   results do not depend on the order of execution.  workspace: ctgcn_pgnn_dist_workspace_bytes() bytes.  Reads a flag back after every pass:
  *   synchronises `stream`.  CTGCN_E_INVALID for bad sizes, null pointers, offsets that do not ascend from 0 to n_members or a member
  *   outside [0, n); CTGCN_E_UNSUPPORTED when n · n_sets reaches 2^31.
@@ -1151,7 +1151,7 @@ int ctgcn_bn_bwd_f32(int64_t n, int32_t d, const float *x, int64_t ldx, const fl
 size_t ctgcn_pgnn_dist_workspace_bytes(void);
 int ctgcn_pgnn_anchor_dist(int64_t n, int64_t nnz, const int32_t *row_ptr, const int32_t *col, int32_t n_sets, const int32_t *offsets,
                            const int32_t *members, int32_t n_members, int32_t cutoff, int32_t *level, float *dist_max, int32_t *pos,
-                           int32_t *node_id, int32_t *levels_run, void *workspace, size_t workspace_bytes, void *stream);
+                           int32_t *node_id, int32_t *levels_run_host, void *workspace, size_t workspace_bytes, void *stream);
 int ctgcn_pgnn_conv_fwd_f32(int64_t n, int32_t n_sets, int32_t d, const float *PS, int64_t ldps, const int32_t *lvl, const float *table,
                             int32_t n_table, const int32_t *idx, const float *w_p, const float *b_p, float *pos, float *strct,
                             int64_t ldstruct, int32_t normalize, float *xraw, double p, uint64_t key, void *stream);
