@@ -28,6 +28,15 @@ except OSError as e:
 
 SIGNATURES, _structs, _const = _cdecl.parse(_header)     # SIGNATURES: name -> (restype, argtypes) of every symbol the header declares
 
+# The top-k link ranking is declared in a header of its own (the entry points of ctgcn_hip.h are a pinned set): same reader, same rules.
+TOPK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ctgcn_topk.h")
+try:
+    with open(TOPK_HEADER_PATH) as _f:
+        _topk = _cdecl.parse(_f.read())
+except OSError as e:
+    raise CtgcnHipError("C header %s not readable (%s): the ctypes binding is derived from it" % (TOPK_HEADER_PATH, e)) from None
+TOPK_SIGNATURES = _topk.functions
+
 
 def _struct(cname):
     return type(cname, (ctypes.Structure,), {"_fields_": _structs[cname], "__doc__": "%s (include/ctgcn_hip.h)" % cname})
@@ -40,6 +49,8 @@ GruSeqGroup = _struct("ctgcn_gru_seq_group_t")
 (ABI_VERSION, F_SELF_LOOP, F_RELU, F_NESTED, ACT_NONE, ACT_SELU, CLS_NODE, CLS_HADAMARD, CLS_DOT, OP_KCORE, OP_INGEST, MAX_SLOTS) = (
     _const["CTGCN_" + k] for k in ("ABI_VERSION", "F_SELF_LOOP", "F_RELU", "F_NESTED", "ACT_NONE", "ACT_SELU", "CLS_NODE", "CLS_HADAMARD",
                                    "CLS_DOT", "OP_KCORE", "OP_INGEST", "MAX_SLOTS"))
+
+TOPK_NO_SELF, TOPK_UPPER = _topk.constants["CTGCN_TOPK_NO_SELF"], _topk.constants["CTGCN_TOPK_UPPER"]      # flags of ctgcn_topk_scores_f32
 
 _lib = None
 
@@ -54,7 +65,7 @@ def load():
             "libctgcn_hip.so not found at %s — the HIP extension is required (no CPU fallback). "
             "Build it with `python -m ctgcn_amd.build`." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(TOPK_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.ctgcn_abi_version() != ABI_VERSION:

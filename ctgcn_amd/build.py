@@ -5,8 +5,9 @@ import subprocess
 import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = [os.path.join(_HERE, "csrc", f) for f in ("ctgcn_hip.hip", "ctgcn_gemm.hip", "ctgcn_gru_bwd.hip", "ctgcn_ingest.hip", "ctgcn_walks.hip", "ctgcn_epoch.hip", "ctgcn_eval.hip", "ctgcn_cent.hip", "ctgcn_nodecls.hip", "ctgcn_sim.hip", "ctgcn_supervised.hip", "ctgcn_gcn.hip", "ctgcn_gat.hip", "ctgcn_pool.hip", "ctgcn_tg.hip", "ctgcn_pgnn.hip", "ctgcn_vgrnn.hip", "ctgcn_dyngem.hip", "ctgcn_lstmcell.hip", "ctgcn_grucell.hip", "ctgcn_timers.hip", "ctgcn_export.cpp")]
+SRCS = [os.path.join(_HERE, "csrc", f) for f in ("ctgcn_hip.hip", "ctgcn_gemm.hip", "ctgcn_gru_bwd.hip", "ctgcn_ingest.hip", "ctgcn_walks.hip", "ctgcn_epoch.hip", "ctgcn_eval.hip", "ctgcn_cent.hip", "ctgcn_nodecls.hip", "ctgcn_sim.hip", "ctgcn_supervised.hip", "ctgcn_gcn.hip", "ctgcn_gat.hip", "ctgcn_pool.hip", "ctgcn_tg.hip", "ctgcn_pgnn.hip", "ctgcn_vgrnn.hip", "ctgcn_dyngem.hip", "ctgcn_lstmcell.hip", "ctgcn_grucell.hip", "ctgcn_timers.hip", "ctgcn_topk.hip", "ctgcn_export.cpp")]
 HDR = os.path.join(os.path.dirname(_HERE), "include", "ctgcn_hip.h")
+TOPK_HDR = os.path.join(os.path.dirname(_HERE), "include", "ctgcn_topk.h")        # the top-k entries: a header of their own
 OUT = os.path.join(_HERE, "csrc", "libctgcn_hip.so")
 STAMP = OUT + ".srchash"          # sha256 of the sources + header + this recipe the .so was built from (travels with it, git-ignored)
 
@@ -15,7 +16,7 @@ def source_hash():
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
     private_hdrs = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))    # every header the kernel files share
-    for f in SRCS + [HDR] + private_hdrs + [os.path.abspath(__file__)]:
+    for f in SRCS + [HDR, TOPK_HDR] + private_hdrs + [os.path.abspath(__file__)]:
         h.update(os.path.basename(f).encode() + b"\0")
         with open(f, "rb") as fh:
             h.update(fh.read())

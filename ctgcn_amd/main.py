@@ -2,8 +2,10 @@
 
     python -m ctgcn_amd.main --config <json> --task <task> [--method <name>]
 
-task is one of preprocessing, embedding, link_pred, node_cls, edge_cls, cent_pred, sim_pred; the config file has the reference's schema
-(config/*.json: one section per task, and per method under 'preprocessing' and 'embedding').  The embedding task runs on the MI355X only:
+task is one of preprocessing, embedding, link_pred, node_cls, edge_cls, cent_pred, sim_pred, graph_recon; the config file has the
+reference's schema (config/*.json: one section per task, and per method under 'preprocessing' and 'embedding').  graph_recon (MAP and
+precision@k over a ranking of all node pairs, evaluation/graph_reconstruction.py) and its config section are this package's own
+extension: the reference has neither.  The embedding task runs on the MI355X only:
 without a visible GPU, or with use_cuda false, it raises CtgcnHipError before anything is loaded.  Unlike the reference this module
 never touches os.environ: which devices a run sees is the caller's choice.
 """
@@ -16,7 +18,7 @@ import torch
 from ._lib import CtgcnHipError
 from .utils import get_supported_methods
 
-TASKS = ('preprocessing', 'embedding', 'link_pred', 'node_cls', 'edge_cls', 'cent_pred', 'sim_pred')
+TASKS = ('preprocessing', 'embedding', 'link_pred', 'node_cls', 'edge_cls', 'cent_pred', 'sim_pred', 'graph_recon')
 _PREPROCESSED = ('GCN', 'GCN_TG', 'GAT', 'GAT_TG', 'SAGE', 'SAGE_TG', 'GIN', 'GIN_TG', 'PGNN', 'CGCN-C', 'GCRN', 'EvolveGCN', 'CTGCN-C')
 
 
@@ -88,8 +90,14 @@ def similarity_prediction_task(args):
     similarity_prediction(args)
 
 
+def graph_reconstruction_task(args):
+    from .evaluation.graph_reconstruction import graph_reconstruction
+    graph_reconstruction(args)
+
+
 _EVALUATION_TASKS = {'link_pred': link_prediction_task, 'node_cls': node_classification_task, 'edge_cls': edge_classification_task,
-                     'cent_pred': centrality_prediction_task, 'sim_pred': similarity_prediction_task}
+                     'cent_pred': centrality_prediction_task, 'sim_pred': similarity_prediction_task,
+                     'graph_recon': graph_reconstruction_task}
 
 
 def main(argv):

@@ -4298,3 +4298,106 @@ def sym_topk(apply, n, k, tol=1e-12, max_iter=5000, seed=0, device=None, _defici
 
 
 sym_topk.last = (0, 0.0)
+
+
+# ------------------------------------------------------------------------------------ top-k link ranking (ctgcn_topk.hip)
+TOPK_TILE = 32                          # query rows of a wave and candidate columns of a tile
+TOPK_MAX_CHUNKS = 256
+_TOPK_WAVES = 1024                      # waves the default col_chunks aims at: four a CU on 256 CUs
+
+
+def topk_max_k():
+    return int(_lib.load().ctgcn_topk_max_k())
+
+
+def topk_max_d():
+    return int(_lib.load().ctgcn_topk_max_d())
+
+
+def _topk_exclusion(exclude, n, dev):
+    """(row_ptr, col) of the exclusion pattern; its shape, device and ascending columns are checked once per GcnAdj"""
+    if not isinstance(exclude, GcnAdj):
+        raise TypeError("exclude must be an ops.GcnAdj, got %s" % type(exclude).__name__)
+    if exclude.n != n:
+        raise ValueError("exclude has %d rows, E has %d" % (exclude.n, n))
+    if exclude.device != dev:
+        raise ValueError("exclude is on %s, E on %s" % (exclude.device, dev))
+    if not getattr(exclude, "_topk_checked", False):
+        if exclude.nnz:
+            col = exclude.col.to(torch.int64)
+            if int(col.min()) < 0 or int(col.max()) >= n:
+                raise ValueError("exclude has a column outside [0, %d)" % n)
+            key = exclude._rows() * n + col
+            if exclude.nnz > 1 and not bool((key[1:] > key[:-1]).all()):
+                raise ValueError("exclude's columns must ascend within every row (sorted, no duplicates)")
+        exclude._topk_checked = True
+    return exclude.row_ptr, exclude.col
+
+
+def topk_scores(E, k, rows=None, row_bias=None, col_bias=None, exclude_self=False, upper_only=False, exclude=None, col_chunks=None):
+    """The k best admissible candidates of every query row by s(i, j) = E[q] · E[j] (+ col_bias[j]) (+ row_bias[i]), q = rows[i] or i:
+    (score float32 [m, k], index int32 [m, k]), each row by score descending and index ascending among equal scores, unused slots
+    -inf / -1.  The score is one ascending fp32 fmaf chain on the matrix cores and the two adds, in that order; the [m, n] matrix is
+    never stored.  exclude_self drops j == q, upper_only j <= q, exclude (a GcnAdj, only its pattern is read) the stored entries of
+    row q.  col_chunks cuts the candidates into that many column ranges swept by different blocks (None: enough to fill the device);
+    the result does not depend on it.  No autograd."""
+    _need_cuda(E, rows, row_bias, col_bias)
+    if E.dtype != torch.float32:
+        raise TypeError("E must be float32, got %s" % E.dtype)
+    if E.dim() != 2:
+        raise ValueError("E must be [n, d]")
+    n, d = E.shape
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1, got %d" % k)
+    if k > topk_max_k():
+        raise ValueError("k = %d above ctgcn_topk_max_k() = %d" % (k, topk_max_k()))
+    if d < 1 or d > topk_max_d():
+        raise ValueError("d = %d outside [1, ctgcn_topk_max_d() = %d]" % (d, topk_max_d()))
+    if n >= 2 ** 31:
+        raise ValueError("n = %d: at most 2^31 - 1 candidates" % n)
+    dev = E.device
+    E = E.detach()
+    if n and (E.stride(1) != 1 or E.stride(0) < d):
+        E = E.contiguous()
+    if rows is not None:
+        if rows.dtype not in (torch.int32, torch.int64):
+            raise TypeError("rows must be int32 or int64, got %s" % rows.dtype)
+        if rows.dim() != 1 or rows.device != dev:
+            raise ValueError("rows must be a vector on E's device")
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n):
+            raise ValueError("rows has an entry outside [0, %d)" % n)
+        rows = _i32(rows)
+        m = rows.numel()
+    else:
+        m = n
+    for name, b, length in (("row_bias", row_bias, m), ("col_bias", col_bias, n)):
+        if b is None:
+            continue
+        if b.dtype != torch.float32:
+            raise TypeError("%s must be float32, got %s" % (name, b.dtype))
+        if b.dim() != 1 or b.numel() != length or b.device != dev:
+            raise ValueError("%s must be a vector of %d entries on E's device" % (name, length))
+    row_bias = None if row_bias is None else row_bias.detach().contiguous()
+    col_bias = None if col_bias is None else col_bias.detach().contiguous()
+    ex_ptr, ex_col = (None, None) if exclude is None else _topk_exclusion(exclude, n, dev)
+    tiles = (n + TOPK_TILE - 1) // TOPK_TILE
+    if col_chunks is None:
+        row_tiles = max(1, (m + TOPK_TILE - 1) // TOPK_TILE)
+        col_chunks = max(1, min((_TOPK_WAVES + row_tiles - 1) // row_tiles, tiles, 64))
+    col_chunks = int(col_chunks)
+    if col_chunks < 1 or col_chunks > TOPK_MAX_CHUNKS:
+        raise ValueError("col_chunks = %d outside [1, %d]" % (col_chunks, TOPK_MAX_CHUNKS))
+    flags = (_lib.TOPK_NO_SELF if exclude_self else 0) | (_lib.TOPK_UPPER if upper_only else 0)
+    score = torch.empty(m, k, dtype=torch.float32, device=dev)
+    index = torch.empty(m, k, dtype=torch.int32, device=dev)
+    if m == 0:
+        return score, index
+    lib = _lib.load()
+    with torch.cuda.device(dev), _timed("topk_scores", m=m, n=n, d=d, k=k, col_chunks=col_chunks):
+        nbytes = int(lib.ctgcn_topk_workspace_bytes(m, n, k, col_chunks))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        check(lib.ctgcn_topk_scores_f32(m, n, d, k, ptr(E), E.stride(0) if n else d, ptr(rows), ptr(row_bias), ptr(col_bias), ptr(ex_ptr),
+                                        ptr(ex_col), flags, col_chunks, ptr(score), ptr(index), ptr(ws), nbytes, _stream()),
+              "ctgcn_topk_scores_f32")
+    return score, index
